@@ -8,13 +8,17 @@ pickers x ~300 boxes, box 180, 4096^2) per GPU; multi-GPU runs shard micrographs
 ranks (weak scaling, no collective in the hot path).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5] [--n_mg M]
+                  [--dump-outputs DIR] [--full]
 
-Prints ONE JSON line on rank 0 (driver contract), with "roofline" (dominant kernel, HIP
-events around each launch) and "cpu_baseline" (the oracle's faithful per-pair loop on a
-bounded sample, 1 core).  Steps are pipelined on three contexts, each on its own stream, so
-that step i+1's workgroups run in step i's drain tail (--streams 1 serialises two contexts on
-one stream); the roofline's per-launch durations then come from serialised steps timed after
-the timed region.
+Prints ONE JSON line on rank 0 (driver contract).  A plain run sets up, warms up, times the K
+steps and prints the headline ("value", "ms_per_step", the workload and its totals);
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs).  --full adds everything that takes runs of its own: "roofline" (dominant
+kernel, HIP events around each launch), "cpu_baseline" (the oracle's faithful per-pair loop on
+a bounded sample, 1 core), "by_config" (the other configs) and "stats_copy_variant".  Steps
+are pipelined on three contexts, each on its own stream, so that step i+1's workgroups run in
+step i's drain tail (--streams 1 serialises two contexts on one stream); the roofline's
+per-launch durations then come from serialised steps timed after the timed region.
 """
 from __future__ import annotations
 
@@ -352,6 +356,11 @@ SER_STEPS = 8    # two-stream runs: serialised steps timed with HIP events for t
 # on its own launch stream, C2 -1.5 %, C4 -1.3 %, C3 -0.6 %, C5 -4.7 % (the large route syncs
 # on the host once per clique level; profiles/r05w_ab_copy_on_stream.txt)
 PIPE_DEPTH_DEFAULT = 3
+# --full: seconds of timed steps per run beside the headline (a by_config entry, the stats-copy
+# variant) before it takes fewer steps than --steps, so that a headline timed over very many of
+# its short steps does not stretch the 100k-micrograph entries to minutes; MIN_STEPS at least
+ENTRY_BUDGET_S = 8.0
+MIN_STEPS = 10
 PIPE_DEPTH = {}
 
 
@@ -411,13 +420,88 @@ def pipelined_steps(ctxs, submit, n, timing, ktimes=None):
     return r
 
 
+DUMP_BUDGET = 48 << 20   # --dump-outputs: bytes of per-clique arrays (the whole dump < 64 MB)
+DUMP_SEED = 0            # ... and the seed of its micrograph sample
+
+
+def _d2h(ptr, n, dtype):
+    """n elements of a device array as numpy (hipMemcpy of the HIP runtime the library itself
+    is linked to, found through the library's handle)"""
+    import ctypes
+
+    from repic_amd import _lib
+    out = np.empty(n, dtype=dtype)
+    if n:
+        rc = _lib.lib.hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(int(ptr)),
+                                ctypes.c_size_t(out.nbytes), ctypes.c_int(2))
+        if rc != 0:
+            raise RuntimeError(f"hipMemcpy (device to host) failed: {rc}")
+    return out
+
+
+def dump_outputs(r, k, out_dir, rank=0):
+    """--dump-outputs: the arrays one step hands its caller (rgc_batch_out of Result ``r``,
+    per-clique arrays in HBM or on the host), as ``out_dir/<name>.npy``:
+
+    * per micrograph, all of them, f64: status, n_nodes, n_vert, n_edges_mg, clique_cnt;
+    * per clique, f32 (consensus: f64, a batch box index): rows [S, k], w, conf, consensus of
+      a fixed sample of micrographs (a seeded permutation's prefix that fits DUMP_BUDGET; all
+      of them when they fit), micrograph by micrograph in ascending micrograph order, each
+      micrograph's cliques in the library's order.  The order of the micrographs' ranges in
+      the library's own arrays is unspecified (rgc_batch_out.clique_base), so it is not kept;
+    * sample_micrographs, f64: the sampled micrographs' indices.
+
+    Ranks other than 0 write ``<name>.rank<r>.npy``.  Returns the bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    cnt = np.array(r.clique_cnt, dtype=np.int64)
+    base = np.array(r.clique_base, dtype=np.int64)
+    per_clique = 4 * k + 16
+    cap = DUMP_BUDGET // per_clique
+    order = np.random.default_rng(DUMP_SEED).permutation(r.n_mg)
+    n_s = int(np.searchsorted(np.cumsum(cnt[order]), cap, side="right"))
+    sample = np.sort(order[:max(n_s, 1)])
+    take = np.minimum(cnt[sample], cap)   # (one micrograph over the budget: its first cliques)
+    on_host = isinstance(r.w, np.ndarray)
+
+    def gather(v, dtype, width):
+        parts = []
+        for b0, n in zip(base[sample].tolist(), take.tolist()):
+            if on_host:
+                parts.append(np.asarray(v).reshape(-1)[b0 * width:(b0 + n) * width])
+            else:
+                parts.append(_d2h(int(v or 0) + b0 * width * np.dtype(dtype).itemsize,
+                                  n * width, dtype))
+        out = np.concatenate(parts) if parts else np.zeros(0, dtype)
+        return out.reshape(-1, width) if width > 1 else out
+
+    arrays = {f: np.array(getattr(r, f), dtype=np.float64)
+              for f in ("status", "n_nodes", "n_vert", "n_edges_mg")}
+    arrays["clique_cnt"] = cnt.astype(np.float64)
+    arrays["sample_micrographs"] = sample.astype(np.float64)
+    arrays["rows"] = gather(r.rows, np.int32, k).astype(np.float32)
+    arrays["w"] = gather(r.w, np.float32, 1)
+    arrays["conf"] = gather(r.conf, np.float32, 1)
+    arrays["consensus"] = gather(r.consensus, np.int32, 1).astype(np.float64)
+    total = 0
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + (f".rank{rank}" if rank else "") + ".npy"), a)
+        total += a.nbytes
+    return total
+
+
 def measure(args, env, config, n_mg, steps, warmup, host_io=False, no_pipeline=False,
-            lazy_stats=True, streams=1, depth=None, entry=None, fixed_total=None):
+            lazy_stats=True, streams=1, depth=None, entry=None, fixed_total=None, full=True,
+            dump_dir=None, budget_s=None):
     """Time ``steps`` steps of the hot path over one synthetic batch of ``config`` (n_mg
     micrographs per rank, inputs resident in HBM; with ``fixed_total``, this rank's share of
     one batch of that many micrographs): barrier + synchronize on both sides, max over ranks.
-    ``entry`` names the workload for its PMC record (default: the config).  Returns (report
-    dict, cfg, this rank's micrographs)."""
+    ``entry`` names the workload for its PMC record (default: the config).  ``dump_dir``: the
+    last timed step's outputs are written there (dump_outputs).  Without ``full`` nothing runs
+    after the timed steps: no serialised leg, so no roofline of overlapping steps, and no
+    micrograph sample for the CPU baseline.  ``budget_s`` (the runs beside the headline, never
+    the headline itself): fewer timed steps than ``steps`` where the warm-up's pace says they
+    would take longer than that, MIN_STEPS at least; the report's "steps" says how many ran.
+    Returns (report dict, cfg, this rank's first micrographs or None)."""
     import torch
 
     from repic_amd import _lib, synth
@@ -437,7 +521,7 @@ def measure(args, env, config, n_mg, steps, warmup, host_io=False, no_pipeline=F
     procs = min(16, len(os.sched_getaffinity(0))) if n_mg * cfg.n_true * cfg.k >= 2_000_000 else 1
     batch = Batch.from_counts(cfg.k, cfg.box, *synth.packed(cfg, n_mg, start=start, procs=procs))
     # the first micrographs as per-picker arrays, for the CPU baseline's sample
-    mgs = synth.batch(cfg, min(n_mg, 64 if config != "C3" else 8), start=start)
+    mgs = synth.batch(cfg, min(n_mg, 64 if config != "C3" else 8), start=start) if full else None
     t_gen = time.time() - t_gen
     # the one exchange of the sharded path: global box-id offsets
     if dist is not None:
@@ -520,7 +604,18 @@ def measure(args, env, config, n_mg, steps, warmup, host_io=False, no_pipeline=F
     overlap = pipeline and streams == 2
     try:
         if warmup:
-            steps_run(warmup, False)
+            steps_run(warmup - 1 if budget_s is not None else warmup, False)
+            if budget_s is not None:
+                # the pace of the last warm-up step alone (no first-run allocations in it)
+                t_w = time.perf_counter()
+                steps_run(1, False)
+                torch.cuda.synchronize()
+                pace = time.perf_counter() - t_w
+                steps = min(steps, max(MIN_STEPS, int(budget_s / pace)))
+                if dist is not None:   # every rank times the same number of steps
+                    t = torch.tensor([steps], dtype=torch.int64, device=cdev)
+                    dist.all_reduce(t, op=dist.ReduceOp.MIN)
+                    steps = int(t.item())
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
@@ -536,8 +631,9 @@ def measure(args, env, config, n_mg, steps, warmup, host_io=False, no_pipeline=F
         elapsed = time.perf_counter() - t0
         N, E, C = int(r.n_boxes), int(r.n_edges), int(r.n_cliques)
         V = int(r.n_vert.sum())
+        dumped = dump_outputs(r, cfg.k, dump_dir, rank) if dump_dir else None
         r = None
-        if overlap:
+        if overlap and full:
             # the roofline's per-launch kernel durations: SER_STEPS steps on one context, one
             # stream, each launch alone on the GPU (HIP events around every kernel)
             ktimes = {"__steps": SER_STEPS}
@@ -560,6 +656,29 @@ def measure(args, env, config, n_mg, steps, warmup, host_io=False, no_pipeline=F
         tot_mg, tot_e, tot_c = n_mg, E, C
 
     value = tot_mg * steps / elapsed
+    out = {
+        "value": value, "unit": "micrographs/s", "n_gpus": world, "steps": steps,
+        "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
+        "config": {"workload": f"{entry}: {dict(synth.CONFIGS[config], **ENTRY_KW.get(entry, {}))}",
+                   "micrographs_per_gpu": n_mg if fixed_total is None else fixed_total / world,
+                   "micrographs_per_step": tot_mg,
+                   "scaling": "weak" if fixed_total is None else "strong",
+                   "k": cfg.k, "box_size": cfg.box,
+                   "boxes_per_gpu": N, "edges_per_gpu": E, "cliques_per_gpu": C,
+                   "parallelism": f"dp{world} (micrograph shards)",
+                   "io": "host buffers over PCIe (--host-io)" if host_io else "HBM-resident",
+                   "steps_in_flight": len(ctxs) if pipeline else 1,
+                   "streams": len(ctxs) if overlap else 1,
+                   "stream_plan": stream_plan(depth)},
+        "edges_per_sec": tot_e * steps / elapsed,
+        "totals": {"micrographs": tot_mg, "edges": tot_e, "cliques": tot_c},
+        "gen_s": t_gen, "gen_procs": procs,
+    }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": dump_dir, "bytes": dumped}
+    if not any(k_ != "__steps" for k_ in ktimes):
+        # no launch carried HIP events (overlapping steps without the serialised leg)
+        return out, cfg, mgs
     nt = ktimes.pop("__steps", steps)   # steps that carried timing events
     avg = {k_: v / nt for k_, v in ktimes.items()}
     dev_ms = sum(v for k_, v in avg.items() if k_ not in ("d2h", "h2d_meta", "d2h_stats"))
@@ -581,22 +700,7 @@ def measure(args, env, config, n_mg, steps, warmup, host_io=False, no_pipeline=F
     kind = "k_fused" if dom == "k_fused" else "route"
     dv_kernel = "k_fused" if kind == "k_fused" else max(avg, key=avg.get)
     traffic, hbm_frac, limiter = roofline_evidence(rec, kind, dom_bytes, dom_ms, dv_kernel)
-    out = {
-        "value": value, "unit": "micrographs/s", "n_gpus": world, "steps": steps,
-        "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
-        "config": {"workload": f"{entry}: {dict(synth.CONFIGS[config], **ENTRY_KW.get(entry, {}))}",
-                   "micrographs_per_gpu": n_mg if fixed_total is None else fixed_total / world,
-                   "micrographs_per_step": tot_mg,
-                   "scaling": "weak" if fixed_total is None else "strong",
-                   "k": cfg.k, "box_size": cfg.box,
-                   "boxes_per_gpu": N, "edges_per_gpu": E, "cliques_per_gpu": C,
-                   "parallelism": f"dp{world} (micrograph shards)",
-                   "io": "host buffers over PCIe (--host-io)" if host_io else "HBM-resident",
-                   "steps_in_flight": len(ctxs) if pipeline else 1,
-                   "streams": len(ctxs) if overlap else 1,
-                   "stream_plan": stream_plan(depth)},
-        "edges_per_sec": tot_e * steps / elapsed,
-        "totals": {"micrographs": tot_mg, "edges": tot_e, "cliques": tot_c},
+    out.update({
         "roofline": {"bound": derived_bound(rec, kind, dom_bytes, dom_ms, dv_kernel),
                      "priced_against": "hbm (no contraction: no MFMA roofline applies)",
                      "kernel": dom, "achieved": achieved,
@@ -621,9 +725,8 @@ def measure(args, env, config, n_mg, steps, warmup, host_io=False, no_pipeline=F
         "pipeline": {"device_ms_per_step": dev_ms, "alg_bytes": pipe,
                      "achieved_gbs": pipe / (dev_ms * 1e-3) / 1e9,
                      "frac": pipe / (dev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     "kernel_ms": {k_: round(v, 4) for k_, v in sorted(avg.items())}},
-        "gen_s": t_gen, "gen_procs": procs,
-    }
+                     "kernel_ms": {k_: round(v, 4) for k_, v in sorted(avg.items())}}
+    })
     return out, cfg, mgs
 
 
@@ -652,6 +755,16 @@ def main():
     ap.add_argument("--config", default="C2")
     ap.add_argument("--n_mg", type=int, default=None, help="micrographs per GPU")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (the "
+                         "headline run's rgc_batch_out) as DIR/<name>.npy, under 64 MB in all: "
+                         "see dump_outputs; same arguments, same inputs, so two builds can be "
+                         "compared array by array")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline, each in runs of its own: the "
+                         "roofline (serialised steps with HIP events), the CPU baselines, "
+                         "by_config (the other configs, file to file included) and "
+                         "stats_copy_variant; the options below that tune these need it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--host-io", action="store_true",
@@ -681,6 +794,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
+    if not args.full and (args.by_config or "none").lower() != "none":
+        sys.exit("bench.py: --by-config needs --full")
     if args.launch_check:   # test hook: the launcher's rank layout, no GPU work
         print(json.dumps({k_: os.environ.get(k_) for k_ in
                           ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR")}), flush=True)
@@ -690,7 +805,7 @@ def main():
     n_mg = args.n_mg or DEFAULT_MG[args.config]
     rep, cfg, mgs = measure(args, env, args.config, n_mg, args.steps, args.warmup,
                             host_io=args.host_io, no_pipeline=args.no_pipeline,
-                            streams=args.streams)
+                            streams=args.streams, full=args.full, dump_dir=args.dump_outputs)
     out = {"metric": "micrographs/sec (get_cliques, whole node) at 1/2/4/8 MI355X; % HBM roofline"}
     out.update(rep)
     out.update({"higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -699,6 +814,13 @@ def main():
                               "(RGC_F_LAZY_STATS, since round 4): each step copies its 128-B "
                               "cursor block; see stats_copy_variant for the rate with every "
                               "step's per-micrograph stats copied to the host"})
+    if not args.full:
+        # a plain run: the headline alone (its set-up, warm-up and timed steps)
+        if env.rank == 0:
+            print(json.dumps(out), flush=True)
+        if env.dist is not None:
+            env.dist.destroy_process_group()
+        return
     # the other BASELINE configs in the same run (same steps / warmup, their bench sizes:
     # C4 at the 100k / 8-GPU shard of 12.5k micrographs per GPU, C4_100k the whole north-star
     # batch on this GPU), each with a 1-core CPU baseline sample on rank 0
@@ -729,7 +851,7 @@ def main():
                 continue
             r_c, cfg_c, mgs_c = measure(args, env, config, n_c, args.steps, args.warmup,
                                         no_pipeline=args.no_pipeline, streams=args.streams,
-                                        entry=name,
+                                        entry=name, budget_s=ENTRY_BUDGET_S,
                                         fixed_total=n_c if name in FIXED_TOTAL else None)
             byc[name] = by_config_entry(r_c)
             if cpu_rank0 and args.by_config_cpu_budget > 0 and not args.no_cpu_baseline:
@@ -750,7 +872,7 @@ def main():
         # the rate with every step's per-micrograph stats copied to the host (what
         # the CLI reads), next to the headline's lazy-stats rate
         r_s, _, _ = measure(args, env, args.config, n_mg, args.steps, args.warmup,
-                            lazy_stats=False, streams=args.streams)
+                            lazy_stats=False, streams=args.streams, budget_s=ENTRY_BUDGET_S)
         out["stats_copy_variant"] = {"value": r_s["value"], "ms_per_step": r_s["ms_per_step"],
                                      "note": "same workload, per-micrograph stats (48 B each) "
                                              "copied to pinned host memory in every step"}

@@ -154,3 +154,91 @@ def test_pmc_record_is_keyed_by_entry(tmp_path, monkeypatch):
     assert bench.pmc_record("C4_100k_fixed") == (None, None)
     assert bench.pmc_record("C2")[1] == "c_c2_traffic.json"
     assert bench.pmc_record("C5_256") == (None, None)
+
+
+def _host_result(cnt, k, seed=0):
+    """A Result-shaped namespace with host per-clique arrays whose micrograph ranges lie in a
+    shuffled order (rgc_batch_out.clique_base: their order is unspecified)."""
+    from types import SimpleNamespace
+
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    cnt = np.asarray(cnt, np.int64)
+    n_mg, C = len(cnt), int(cnt.sum())
+    perm = rng.permutation(n_mg)
+    base = np.zeros(n_mg, np.int64)
+    base[perm] = np.cumsum(cnt[perm]) - cnt[perm]
+    owner = np.zeros(C, np.int64)
+    for m in range(n_mg):
+        owner[base[m]:base[m] + cnt[m]] = m
+    within = np.arange(C) - base[owner]
+    return SimpleNamespace(
+        n_mg=n_mg, clique_cnt=cnt, clique_base=base, status=np.zeros(n_mg, np.int32),
+        n_nodes=np.arange(n_mg, dtype=np.int32), n_vert=np.arange(n_mg, dtype=np.int32) + 7,
+        n_edges_mg=np.arange(n_mg, dtype=np.int64) * 3,
+        rows=(owner[:, None] * 100 + within[:, None] + np.arange(k)[None, :]).astype(np.int32),
+        w=(owner + within / 1000.0).astype(np.float32), conf=rng.random(C).astype(np.float32),
+        consensus=(owner * 1000 + within).astype(np.int32)), owner, within
+
+
+def test_dump_outputs_layout_and_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: every per-micrograph array in full; the per-clique arrays of the
+    sampled micrographs in ascending micrograph order whatever the order of their ranges, each
+    micrograph's cliques in the library's order; f32 / f64 only; a budget smaller than the
+    batch gives the same seeded sample every time, and one smaller than a single micrograph
+    that micrograph's first cliques."""
+    import numpy as np
+    k = 3
+    cnt = [5, 0, 9, 4, 7, 1, 6, 3]
+    r, owner, within = _host_result(cnt, k)
+    d = tmp_path / "all"
+    n = bench.dump_outputs(r, k, str(d))
+    got = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert set(got) == {"status", "n_nodes", "n_vert", "n_edges_mg", "clique_cnt",
+                        "sample_micrographs", "rows", "w", "conf", "consensus"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert n == sum(a.nbytes for a in got.values())
+    assert np.array_equal(got["sample_micrographs"], np.arange(len(cnt)))
+    assert np.array_equal(got["clique_cnt"], cnt) and np.array_equal(got["n_vert"], r.n_vert)
+    want_owner = np.repeat(np.arange(len(cnt)), cnt)
+    want_within = np.concatenate([np.arange(c) for c in cnt])
+    assert np.array_equal(got["consensus"], want_owner * 1000 + want_within)
+    assert np.array_equal(got["rows"], (want_owner[:, None] * 100 + want_within[:, None]
+                                        + np.arange(k)[None, :]).astype(np.float32))
+    o = np.lexsort((within, owner))
+    assert np.array_equal(got["w"], r.w[o]) and np.array_equal(got["conf"], r.conf[o])
+    # another order of the ranges, same content: the same dump
+    r2, _, _ = _host_result(cnt, k, seed=5)
+    bench.dump_outputs(r2, k, str(tmp_path / "perm"))
+    for name in ("rows", "w", "consensus", "clique_cnt"):
+        assert np.array_equal(np.load(tmp_path / "perm" / (name + ".npy")), got[name]), name
+    # a budget of 12 cliques: a fixed sample of whole micrographs
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 12 * (4 * k + 16))
+    picks = []
+    for t in ("s1", "s2"):
+        bench.dump_outputs(r, k, str(tmp_path / t))
+        picks.append(np.load(tmp_path / t / "sample_micrographs.npy").astype(int))
+        assert len(np.load(tmp_path / t / "w.npy")) == sum(cnt[m] for m in picks[-1]) <= 12
+    assert np.array_equal(picks[0], picks[1]) and 0 < len(picks[0]) < len(cnt)
+    assert np.array_equal(np.load(tmp_path / "s1" / "clique_cnt.npy"), cnt)
+    # a budget below one micrograph: its first cliques; other ranks' files carry the rank
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 2 * (4 * k + 16))
+    r3, _, _ = _host_result([9, 9, 9], k)
+    bench.dump_outputs(r3, k, str(tmp_path / "one"), rank=1)
+    m = np.load(tmp_path / "one" / "sample_micrographs.rank1.npy").astype(int)
+    assert len(m) == 1
+    assert np.array_equal(np.load(tmp_path / "one" / "consensus.rank1.npy"),
+                          m[0] * 1000 + np.arange(2))
+
+
+def test_plain_run_refuses_what_needs_full():
+    """--by-config entries are timed only with --full: a plain run that names some is an
+    error before any GPU work ('none' is accepted)."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--by-config", "C3",
+                        "--launch-check"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--full" in r.stderr
+    for extra in (["--by-config", "none"], ["--full", "--by-config", "C3"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--launch-check"]
+                           + extra, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr

@@ -232,14 +232,14 @@ def test_bench_two_ranks_one_gpu():
 
 @pytest.mark.gpu
 def test_bench_fixed_batch_two_ranks():
-    """The strong-scaling entry: `bench.py --gpus 2 --by-config C4_100k_fixed` (two
+    """The strong-scaling entry: `bench.py --gpus 2 --full --by-config C4_100k_fixed` (two
     self-spawned ranks on cuda:0 over gloo) splits ONE 100k-micrograph C4 batch 50k / 50k and
     reports its total of 100k micrographs per step, scaling "strong"."""
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(RGC_BENCH_DEVICE="0", RGC_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
-                        "--config", "C2", "--n_mg", "20", "--by-config", "C4_100k_fixed",
+                        "--config", "C2", "--n_mg", "20", "--full", "--by-config", "C4_100k_fixed",
                         "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], env=env,
                        capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -1,5 +1,5 @@
 #!/bin/bash
-# All GPU tests, smoke, then the default bench line (the driver's command).  First failure
+# All GPU tests, smoke, then the full bench line (--full: by_config, roofline, CPU baselines).  First failure
 # ends the script.
 #   gpurun --timeout 1200 -- bash tools/gpu_check.sh TAG
 set -e -o pipefail
@@ -13,7 +13,7 @@ tail -1 "$OUT/pytest_gpu.log"
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 \
   || { tail -30 "$OUT/smoke.log"; exit 1; }
 tail -1 "$OUT/smoke.log"
-timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" \
+timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench.json" 2> "$OUT/bench.err" \
   || { tail -30 "$OUT/bench.err"; exit 1; }
 python3 - "$OUT/bench.json" <<'PY'
 import json, sys

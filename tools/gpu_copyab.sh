@@ -8,7 +8,7 @@ set -e -o pipefail
 OUT=gpurun_out/${1:-copyab}; mkdir -p $OUT
 for r in 1 2; do
   for mode in null high; do
-    RGC_BENCH_COPY=$mode timeout -k 10 200 python3 -u bench.py --by-config none --no-cpu-baseline --steps 20 --warmup 5 > $OUT/b_${mode}_$r.json 2> $OUT/b_${mode}_$r.err || { tail -20 $OUT/b_${mode}_$r.err; exit 1; }
+    RGC_BENCH_COPY=$mode timeout -k 10 200 python3 -u bench.py --full --by-config none --no-cpu-baseline --steps 20 --warmup 5 > $OUT/b_${mode}_$r.json 2> $OUT/b_${mode}_$r.err || { tail -20 $OUT/b_${mode}_$r.err; exit 1; }
     python3 -c "import json,sys; d=json.load(open('$OUT/b_${mode}_$r.json')); print('$mode', $r, round(d['value']), round(d['stats_copy_variant']['value']), round(d['stats_copy_variant']['ms_per_step'],4))"
   done
 done

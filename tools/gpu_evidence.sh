@@ -25,7 +25,7 @@ for C in $CFGS; do
 done
 for C in $CFGS; do
   echo "== $C bench + cpu baseline"
-  timeout -k 10 400 python3 -u bench.py --config $C --by-config none > "$OUT/bench_$C.json" 2> "$OUT/bench_$C.err" \
+  timeout -k 10 400 python3 -u bench.py --config $C --full --by-config none > "$OUT/bench_$C.json" 2> "$OUT/bench_$C.err" \
     || { tail -30 "$OUT/bench_$C.err"; exit 1; }
   python3 -c "import json;d=json.load(open('$OUT/bench_$C.json'));r=d['roofline'];print('$C', round(d['value']), round(d['ms_per_step'],4), round(r['frac'],4), d.get('cpu_baseline',{}).get('value'))"
 done

@@ -7,7 +7,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 run() {  # config wgcap
   local C=$1 W=$2
-  RGC_DIAG_MAX_WG=$W timeout -k 10 200 python -u bench.py --config $C --no-cpu-baseline --steps 20 --warmup 5 \
+  RGC_DIAG_MAX_WG=$W timeout -k 10 200 python -u bench.py --config $C --full --no-cpu-baseline --steps 20 --warmup 5 \
     > "$OUT/b_${C}_$W.json" 2> "$OUT/b_${C}_$W.err" || { tail -20 "$OUT/b_${C}_$W.err"; exit 1; }
   python3 -c "import json;d=json.load(open('$OUT/b_${C}_$W.json'));print('$C wg<=$W', round(d['value']), d['pipeline']['kernel_ms'])"
 }

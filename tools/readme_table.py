@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""README / DESIGN measurement table from a bench.py line with by_config (one JSON line).
+"""README / DESIGN measurement table from a `bench.py --full` line with by_config (one JSON line).
 
   python tools/readme_table.py profiles/r04z_bench_default.json
 """
