@@ -15,6 +15,11 @@
  *                       cliques (:49-56,:160-161), ILP weight / confidence / consensus
  *                       (:164-190) and constraint-matrix COO (:192-202), for a whole
  *                       batch of micrographs at once.
+ *   rgc_ilp_solve    <- run_ilp.py:50-63 (the set packing, exact, instead of Gurobi)
+ *   rgc_consensus    <- get_cliques.py:134-202 followed by run_ilp.py:50-124 without the
+ *                       files in between (ABI 10): rgc_run, the solver and the ordered picks
+ *                       in one call, the per-clique arrays staying in HBM
+ *   rgc_write_boxes  <- run_ilp.py:126-133 (the final <base>.box of each micrograph; ABI 10)
  *
  * Conventions: plain pointers and sizes, no torch types.  Returns 0 on success and a
  * negative code on error (message in rgc_last_error(), thread-local).  Outputs are owned
@@ -29,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RGC_ABI_VERSION 9
+#define RGC_ABI_VERSION 10
 
 /* flags for rgc_batch_in.flags */
 #define RGC_F_GET_CC         1u  /* --get_cc   (get_cliques.py:151-156) */
@@ -222,6 +227,69 @@ typedef struct rgc_ilp_in {
 } rgc_ilp_in;
 int rgc_ilp_solve(rgc_ctx* ctx, const rgc_ilp_in* in, uint8_t* x, uint8_t* exact);
 
+/* ABI 10 — `repic consensus`: get_cliques and run_ilp in one device pass.  rgc_consensus does
+ * rgc_run's work (both routes, RGC_F_GET_CC, host or device inputs), turns the per-clique
+ * outputs into the solver's inputs on the device (rgc_pick.hip k_pick_cols: the rows, weights,
+ * confidences and consensus ids never leave HBM), solves the set packing of every micrograph
+ * as rgc_ilp_solve does, and emits the picked particles (k_pick_emit) in the order of
+ * run_ilp.py:121-131: confidence descending (compared as floats, +0.0 == -0.0), equal
+ * confidences in ascending column order, coordinates rounded with np.rint (half to even).
+ * Columns are packed micrograph by micrograph, so the result does not depend on the order in
+ * which the clique ranges were reserved.  Micrographs with status != RGC_OK have no columns
+ * and no picks.  RGC_F_MULTI_OUT is rejected (the reference's run_ilp raises on such inputs);
+ * fails like rgc_ilp_solve while a submitted run awaits rgc_wait.  With RGC_F_TIMING (batch
+ * or opts flags) rgc_kernel_times lists rgc_run's sections, then "k_pick_cols", the solver's
+ * sections and "k_pick_emit". */
+typedef struct rgc_consensus_opts {
+  int64_t node_limit;      /* as rgc_ilp_in.node_limit (0: RGC_ILP_DEFAULT_NODES) */
+  int64_t num_particles;   /* keep the first N picks of each micrograph (run_ilp.py:129); < 0:
+                              all; 0: none */
+  uint32_t flags;          /* RGC_F_TIMING */
+} rgc_consensus_opts;
+
+typedef struct rgc_consensus_out {
+  rgc_batch_out run;       /* exactly what rgc_run returns for the batch (per-clique pointers:
+                              device, or host with RGC_F_HOST_OUTPUTS; valid until the next
+                              run on the context) */
+  int64_t n_picked;        /* = pick_off[n_mg] */
+  /* host memory, owned by the context like run's per-micrograph arrays */
+  int64_t* pick_off;       /* [n_mg+1] picks of micrograph m: [pick_off[m], pick_off[m+1]) */
+  double* px;              /* [n_picked] np.rint(consensus x) */
+  double* py;
+  float* pconf;            /* [n_picked] confidence of the picked clique */
+  int32_t* pcol;           /* [n_picked] its column within the micrograph's clique range */
+  int32_t* sel_cnt;        /* [n_mg] columns chosen by the packing, before num_particles */
+  int32_t* ilp_status;     /* [n_mg] RGC_ILP_*: OPTIMAL when every conflict component was
+                              proven; else GAP_OK when the summed component gaps are within
+                              1e-4 of the objective; else the weakest component status */
+  double* ilp_gap;         /* [n_mg] summed component gaps / objective */
+  int64_t h2d_bytes;       /* bytes this call copied host -> device and device -> host */
+  int64_t d2h_bytes;
+} rgc_consensus_out;
+int rgc_consensus(rgc_ctx* ctx, const rgc_batch_in* in, const rgc_consensus_opts* opts,
+                  rgc_consensus_out* out);
+
+/* The emit stage alone, on host arrays (uploaded, run, copied back): test hook of
+ * k_pick_select / k_pick_emit.  Outputs are owned by the context (valid until its next call). */
+typedef struct rgc_pick_in {
+  int32_t n_mg;
+  const int64_t* col_off;  /* [n_mg+1] columns of micrograph m */
+  const uint8_t* x;        /* [n_cols] the packing */
+  const float* conf;       /* [n_cols] */
+  const double* cx;        /* [n_cols] consensus coordinates of each column */
+  const double* cy;
+  int64_t num_particles;   /* < 0: all */
+} rgc_pick_in;
+typedef struct rgc_pick_out {
+  int64_t n_picked;
+  int64_t* pick_off;       /* [n_mg+1] */
+  double* px;
+  double* py;
+  float* pconf;
+  int32_t* pcol;
+} rgc_pick_out;
+int rgc_pick_select(rgc_ctx* ctx, const rgc_pick_in* in, rgc_pick_out* out);
+
 int rgc_parse_files(const char* const* paths, int64_t n_files, int n_threads, rgc_parsed** out);
 void rgc_parsed_free(rgc_parsed* p);
 
@@ -266,6 +334,28 @@ int rgc_pickle_bytes(const rgc_pickle_fmt* fmt, const rgc_write_in* in, int mg, 
                      uint8_t* buf, int64_t cap, int64_t* len);
 /* CPython str(float) (test hook of the runtime.tsv formatting); returns the length. */
 int rgc_py_float_repr(double v, char* buf, int cap);
+
+/* ABI 10 — the consensus BOX writer (reference run_ilp.py:126-133): one <base>.box per
+ * micrograph from rgc_consensus' pick arrays, lines "<x>\t<y>\t<box>\t<box>\t<conf>\n" with
+ * <x>, <y> as str(int(np.rint(v))) prints them (-0.0 -> "0") and <conf> as str(np.float32(v))
+ * (rgc_np_float_str).  A micrograph with count -1 (skipped) or 0 gets an empty file. */
+typedef struct rgc_box_write_in {
+  const char* out_dir;
+  int32_t n_mg;
+  int64_t box_size;
+  const char* const* bases;   /* [n_mg] output base names */
+  const int64_t* pick_off;    /* [n_mg] first pick of each micrograph */
+  const int64_t* count;       /* [n_mg] picks, or -1: skipped micrograph */
+  const double* px;           /* already rounded (np.rint) */
+  const double* py;
+  const float* pconf;
+} rgc_box_write_in;
+/* n_threads threads; on an I/O error returns -errno and the lowest failing micrograph. */
+int rgc_write_boxes(const rgc_box_write_in* in, int n_threads, int64_t* failed_mg);
+/* str(numpy.float32(v)) (test hook of the .box confidence column): shortest round-trip float32
+ * digits, positional for 1e-4 <= |v| < 1e16 (and 0), else scientific with an exponent of at
+ * least two digits; returns the length. */
+int rgc_np_float_str(float v, char* buf, int cap);
 
 /* Host test hooks for the CPython set-order emulation (pyset.h). */
 uint64_t rgc_py_hash_node(double x, double y, int64_t id);

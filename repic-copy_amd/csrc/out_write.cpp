@@ -15,6 +15,10 @@
 // bytes with pickle.dumps of the same objects (frame stripped); the unchanged consumer
 // (run_ilp.py:29-80) unpickles identical objects.  No GIL, no interpreter per file: threads
 // write whole micrographs.
+//
+// Also the BOX writer of `repic consensus` (rgc_write_boxes, reference run_ilp.py:126-133):
+//   <base>.box   "<x>\t<y>\t<box>\t<box>\t<conf>\n" per picked particle, <x> / <y> as
+//                str(int(np.rint(v))) and <conf> as str(numpy.float32(v)) print them.
 #include <cerrno>
 #include <charconv>
 #include <cmath>
@@ -345,6 +349,115 @@ extern "C" int rgc_write_outputs(const rgc_pickle_fmt* fmt, const rgc_write_in* 
                                 "\t" + std::to_string(in->cc_cnt[m]) + "\n";
         e = write_file(base + "_runtime.tsv", tsv);
       }
+      if (e) {
+        err[(size_t)t] = e;
+        bad[(size_t)t] = m;
+        return;
+      }
+    }
+  };
+  if (nt == 1) {
+    work(0);
+  } else {
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t) th.emplace_back(work, t);
+    for (auto& x : th) x.join();
+  }
+  for (int t = 0; t < nt; ++t)
+    if (err[(size_t)t]) {
+      if (failed_mg) *failed_mg = bad[(size_t)t];
+      return err[(size_t)t];
+    }
+  return 0;
+}
+
+namespace {
+
+// str(numpy.float32(v)): numpy's Dragon4 in unique mode gives the shortest digits that round
+// back to the float32 (std::to_chars<float> gives the same digits); positional when
+// 1e-4 <= |v| < 1e16 (compared in double, as numpy does) or v == 0, with at least ".0",
+// else d[.ddd]e+XX with an exponent of at least two digits.
+std::string np_float32(float v) {
+  if (std::isnan(v)) return "nan";
+  if (std::isinf(v)) return v > 0 ? "inf" : "-inf";
+  char buf[64];
+  auto r = std::to_chars(buf, buf + sizeof(buf), v, std::chars_format::scientific);
+  std::string s(buf, r.ptr);
+  const size_t e = s.find('e');
+  std::string mant = s.substr(0, e);
+  const int ex = atoi(s.c_str() + e + 1);
+  bool neg = false;
+  if (!mant.empty() && mant[0] == '-') { neg = true; mant.erase(0, 1); }
+  std::string dig;
+  for (char ch : mant)
+    if (ch != '.') dig.push_back(ch);
+  const double a = std::fabs((double)v);
+  const int decpt = ex + 1;   // value = 0.DIGITS x 10^decpt
+  std::string out;
+  if (a == 0.0 || (a < 1.e16 && a >= 1.e-4)) {
+    if (decpt <= 0) {
+      out = "0." + std::string((size_t)(-decpt), '0') + dig;
+    } else if ((int)dig.size() <= decpt) {
+      out = dig + std::string((size_t)(decpt - (int)dig.size()), '0') + ".0";
+    } else {
+      out = dig.substr(0, (size_t)decpt) + "." + dig.substr((size_t)decpt);
+    }
+  } else {
+    out = dig.substr(0, 1);
+    if (dig.size() > 1) out += "." + dig.substr(1);
+    char eb[16];
+    snprintf(eb, sizeof(eb), "e%c%02d", ex < 0 ? '-' : '+', ex < 0 ? -ex : ex);
+    out += eb;
+  }
+  return neg ? "-" + out : out;
+}
+
+// str(int(v)) of an integral double (-0.0 -> "0")
+void append_int(std::string& o, double v) {
+  if (std::fabs(v) < 9.0e18) {
+    o += std::to_string((long long)v);
+  } else {
+    char b[400];
+    snprintf(b, sizeof(b), "%.0f", v);
+    o += b;
+  }
+}
+
+}  // namespace
+
+extern "C" int rgc_np_float_str(float v, char* buf, int cap) {
+  const std::string s = np_float32(v);
+  if (!buf || (int)s.size() + 1 > cap) return -1;
+  memcpy(buf, s.c_str(), s.size() + 1);
+  return (int)s.size();
+}
+
+extern "C" int rgc_write_boxes(const rgc_box_write_in* in, int n_threads, int64_t* failed_mg) {
+  if (!in || !in->out_dir) return -1;
+  const int n = in->n_mg;
+  if (failed_mg) *failed_mg = -1;
+  if (n <= 0) return 0;
+  const int nt = std::max(1, std::min(n_threads, n));
+  std::vector<int> err((size_t)nt, 0);
+  std::vector<int64_t> bad((size_t)nt, -1);
+  const std::string dir = std::string(in->out_dir) + "/";
+  const std::string box = "\t" + std::to_string((long long)in->box_size) + "\t" +
+                          std::to_string((long long)in->box_size) + "\t";
+  auto work = [&](int t) {
+    std::string o;
+    const int m0 = (int)((int64_t)n * t / nt), m1 = (int)((int64_t)n * (t + 1) / nt);
+    for (int m = m0; m < m1; ++m) {
+      o.clear();
+      const int64_t p0 = in->pick_off[m], cnt = in->count[m];
+      for (int64_t i = 0; i < cnt; ++i) {
+        append_int(o, in->px[p0 + i]);
+        o.push_back('\t');
+        append_int(o, in->py[p0 + i]);
+        o += box;
+        o += np_float32(in->pconf[p0 + i]);
+        o.push_back('\n');
+      }
+      const int e = write_file(dir + in->bases[m] + ".box", o);
       if (e) {
         err[(size_t)t] = e;
         bad[(size_t)t] = m;

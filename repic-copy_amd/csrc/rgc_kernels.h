@@ -362,4 +362,43 @@ void launch_ilp(hipStream_t stream, int phase, const IlpArgs& A, int n_big, int 
 // wave components' multipliers (cert 3), 7 best multipliers -> lam
 void launch_ilp_cert(hipStream_t stream, int phase, const IlpArgs& A);
 
+// consensus hand-off (rgc_pick.hip): rgc_run's per-clique outputs -> the solver's CSC inputs,
+// and after the solve the picked particles of every micrograph.  Columns are packed micrograph
+// by micrograph: micrograph m owns columns [col_off[m], col_off[m + 1]), whose per-clique data
+// start at src_base[m] (nullptr: at col_off[m], the rgc_pick_select test hook).
+struct PickArgs {
+  int n_mg, k;
+  int64_t n_cols;
+  int64_t num_particles;      // ranks kept per micrograph (< 0: all)
+  const int64_t* col_off;     // [n_mg + 1]
+  const int64_t* src_base;    // [n_mg] clique_base of rgc_run, or nullptr
+  const int64_t* row_base;    // [n_mg] exclusive sum of n_vert (k_pick_cols)
+  const int32_t* rows;        // [C * k] micrograph-local rows, ascending (k_pick_cols)
+  const float* w;             // [C] (nullptr in the test hook: primal stays 0)
+  const float* conf;          // [C]
+  const int32_t* cons;        // [C] box of the consensus coordinates, or nullptr: bx / by are
+                              // per clique
+  const double* bx;
+  const double* by;
+  const uint8_t* x;           // [n_cols] the packing
+  // k_pick_cols outputs (the solver's inputs)
+  int64_t* col_ptr;           // [n_cols + 1]
+  int32_t* row_idx;           // [n_cols * k]
+  double* w64;                // [n_cols]
+  int32_t* col_mg;            // [n_cols]
+  // k_pick_select / k_pick_scan outputs
+  int32_t* sel;               // [n_cols] selected columns of each micrograph, ascending
+  int32_t* sel_cnt;           // [n_mg]
+  double* primal;             // [n_mg] sum of w over the selected columns
+  int64_t* pick_off;          // [n_mg + 1]
+  // k_pick_emit outputs, [pick_off[n_mg]]
+  double* px;
+  double* py;
+  float* pconf;
+  int32_t* pcol;
+};
+void launch_pick_cols(hipStream_t stream, const PickArgs& A);
+void launch_pick_select(hipStream_t stream, const PickArgs& A);   // + the pick_off scan
+void launch_pick_emit(hipStream_t stream, const PickArgs& A);
+
 }  // namespace rgc

@@ -73,7 +73,41 @@ class WriteIn(C.Structure):
                 ("cid", C.c_void_p)]
 
 
+class ConsensusOpts(C.Structure):
+    _fields_ = [("node_limit", C.c_int64), ("num_particles", C.c_int64), ("flags", C.c_uint32)]
+
+
+class ConsensusOut(C.Structure):
+    _fields_ = [("run", BatchOut), ("n_picked", C.c_int64), ("pick_off", _i64p),
+                ("px", _f64p), ("py", _f64p), ("pconf", _f32p), ("pcol", _i32p),
+                ("sel_cnt", _i32p), ("ilp_status", _i32p), ("ilp_gap", _f64p),
+                ("h2d_bytes", C.c_int64), ("d2h_bytes", C.c_int64)]
+
+
+class PickIn(C.Structure):
+    _fields_ = [("n_mg", C.c_int32), ("col_off", C.c_void_p), ("x", C.c_void_p),
+                ("conf", C.c_void_p), ("cx", C.c_void_p), ("cy", C.c_void_p),
+                ("num_particles", C.c_int64)]
+
+
+class PickOut(C.Structure):
+    _fields_ = [("n_picked", C.c_int64), ("pick_off", _i64p), ("px", _f64p), ("py", _f64p),
+                ("pconf", _f32p), ("pcol", _i32p)]
+
+
+class BoxWriteIn(C.Structure):
+    _fields_ = [("out_dir", C.c_char_p), ("n_mg", C.c_int32), ("box_size", C.c_int64),
+                ("bases", C.POINTER(C.c_char_p)), ("pick_off", C.c_void_p),
+                ("count", C.c_void_p), ("px", C.c_void_p), ("py", C.c_void_p),
+                ("pconf", C.c_void_p)]
+
+
 lib.rgc_abi_version.restype = C.c_int
+lib.rgc_consensus.argtypes = [C.c_void_p, C.POINTER(BatchIn), C.POINTER(ConsensusOpts),
+                              C.POINTER(ConsensusOut)]
+lib.rgc_pick_select.argtypes = [C.c_void_p, C.POINTER(PickIn), C.POINTER(PickOut)]
+lib.rgc_write_boxes.argtypes = [C.POINTER(BoxWriteIn), C.c_int, C.POINTER(C.c_int64)]
+lib.rgc_np_float_str.argtypes = [C.c_float, C.c_char_p, C.c_int]
 lib.rgc_last_error.restype = C.c_char_p
 lib.rgc_device_count.argtypes = [C.POINTER(C.c_int)]
 lib.rgc_ctx_create.argtypes = [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
@@ -112,7 +146,8 @@ EXPORTS = ["rgc_abi_version", "rgc_last_error", "rgc_device_count", "rgc_ctx_cre
            "rgc_ctx_destroy", "rgc_ctx_set_copy_stream", "rgc_run", "rgc_submit", "rgc_wait", "rgc_fetch_stats", "rgc_detach_host", "rgc_host_block_free", "rgc_kernel_times", "rgc_last_edges", "rgc_parse_files",
            "rgc_parsed_free", "rgc_py_hash_node", "rgc_py_set_order", "rgc_test_epilogue",
            "rgc_score_pairs", "rgc_ilp_solve", "rgc_write_outputs", "rgc_pickle_bytes",
-           "rgc_py_float_repr"]
+           "rgc_py_float_repr", "rgc_consensus", "rgc_pick_select", "rgc_write_boxes",
+           "rgc_np_float_str"]
 
 
 class RGCError(RuntimeError):
@@ -355,6 +390,44 @@ class Context:
                      px, py, ps, dbo, did)
         return bi, keep, flags
 
+    def consensus(self, n_mg, k, box_size, box_off, id_base, x, y, score, flags=0,
+                  dev_meta=None, node_limit=0, num_particles=None, timing=False):
+        """get_cliques + run_ilp in one device pass (rgc_consensus, ABI 10): ``run``'s
+        arguments, then the solver's ``node_limit`` and run_ilp's ``num_particles`` (None:
+        all).  The per-clique arrays stay in HBM unless ``flags`` has ``F_HOST_OUTPUTS``.
+        Returns a :class:`ConsensusResult` (plain copies of the pick arrays)."""
+        bi, keep, flags = self._batch_in(n_mg, k, box_size, box_off, id_base, x, y, score, flags,
+                                         dev_meta)
+        self._retire()
+        opts = ConsensusOpts(int(node_limit), -1 if num_particles is None else int(num_particles),
+                             F_TIMING if timing else 0)
+        co = ConsensusOut()
+        _check(lib.rgc_consensus(self._p, C.byref(bi), C.byref(opts), C.byref(co)))
+        del keep
+        return ConsensusResult(co, self._result(co.run, n_mg, k, flags), n_mg)
+
+    def pick_select(self, col_off, x, conf, cx, cy, num_particles=None):
+        """Test hook of the emit kernels (rgc_pick_select): per micrograph (columns
+        ``col_off[m]:col_off[m+1]``) the columns with x == 1 by confidence descending, equal
+        confidences in column order -> (pick_off, px, py, pconf, pcol) copies."""
+        col_off = np.ascontiguousarray(col_off, np.int64)
+        x = np.ascontiguousarray(x, np.uint8)
+        conf = np.ascontiguousarray(conf, np.float32)
+        cx = np.ascontiguousarray(cx, np.float64)
+        cy = np.ascontiguousarray(cy, np.float64)
+        n_mg = len(col_off) - 1
+        nc = int(col_off[-1])
+        assert n_mg >= 0 and len(x) == len(conf) == len(cx) == len(cy) == nc
+        pi = PickIn(n_mg, col_off.ctypes.data, x.ctypes.data, conf.ctypes.data, cx.ctypes.data,
+                    cy.ctypes.data, -1 if num_particles is None else int(num_particles))
+        po = PickOut()
+        self._retire()
+        _check(lib.rgc_pick_select(self._p, C.byref(pi), C.byref(po)))
+        n = int(po.n_picked)
+        return (_copy(po.pick_off, n_mg + 1, np.int64), _copy(po.px, n, np.float64),
+                _copy(po.py, n, np.float64), _copy(po.pconf, n, np.float32),
+                _copy(po.pcol, n, np.int32))
+
     def last_edges(self):
         """Test hook: (u, v, ji) copies of the JI > 0.3 edges of the last run with F_EDGES
         (batch box indices; order unspecified)."""
@@ -372,6 +445,63 @@ class Context:
         names = (C.c_char_p * max(n, 1))()
         lib.rgc_kernel_times(self._p, n, ms, names)
         return [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+
+def _copy(p, n, dt):
+    """numpy copy of n elements at ctypes pointer p (empty when n == 0 or p is NULL)."""
+    if not n or not p:
+        return np.zeros(0, dt)
+    return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True)
+
+
+class ConsensusResult:
+    """One rgc_consensus call: ``run`` is the :class:`Result` rgc_run would have returned;
+    the rest are copies.  Picks of micrograph m: ``pick_off[m]:pick_off[m+1]`` of ``px``,
+    ``py`` (np.rint of the consensus coordinates), ``pconf`` and ``pcol`` (the column in the
+    micrograph's clique range), in run_ilp's output order.  ``sel_cnt`` counts the chosen
+    columns before ``num_particles``; ``ilp_status`` / ``ilp_gap`` are the micrograph's
+    certification (repic_amd.ilp.mg_status) and relative gap."""
+
+    def __init__(self, co: ConsensusOut, run, n_mg):
+        self.run = run
+        self.n_picked = int(co.n_picked)
+        self.pick_off = (_copy(co.pick_off, n_mg + 1, np.int64) if n_mg
+                         else np.zeros(1, np.int64))
+        self.px = _copy(co.px, self.n_picked, np.float64)
+        self.py = _copy(co.py, self.n_picked, np.float64)
+        self.pconf = _copy(co.pconf, self.n_picked, np.float32)
+        self.pcol = _copy(co.pcol, self.n_picked, np.int32)
+        self.sel_cnt = _copy(co.sel_cnt, n_mg, np.int32)
+        self.ilp_status = _copy(co.ilp_status, n_mg, np.int32)
+        self.ilp_gap = _copy(co.ilp_gap, n_mg, np.float64)
+        self.h2d_bytes, self.d2h_bytes = int(co.h2d_bytes), int(co.d2h_bytes)
+
+
+def write_boxes(out_dir, bases, box_size, pick_off, count, px, py, pconf, n_threads=1):
+    """One ``<base>.box`` per micrograph from pick arrays (rgc_write_boxes, run_ilp.py:126-133);
+    ``count[m]`` = -1 writes the empty file of a skipped micrograph."""
+    n = len(bases)
+    arrs = [np.ascontiguousarray(pick_off, np.int64), np.ascontiguousarray(count, np.int64),
+            np.ascontiguousarray(px, np.float64), np.ascontiguousarray(py, np.float64),
+            np.ascontiguousarray(pconf, np.float32)]
+    assert len(arrs[0]) >= n and len(arrs[1]) == n
+    bs = (C.c_char_p * max(1, n))(*[os.fsencode(b) for b in bases])
+    wi = BoxWriteIn(os.fsencode(out_dir), n, int(box_size), bs, *[a.ctypes.data for a in arrs])
+    bad = C.c_int64(-1)
+    rc = lib.rgc_write_boxes(C.byref(wi), int(n_threads), C.byref(bad))
+    if rc != 0:
+        b = bases[bad.value] if 0 <= bad.value < n else ""
+        raise OSError(-rc, os.strerror(-rc) if rc < -1 else "rgc_write_boxes failed",
+                      os.path.join(out_dir, b + ".box"))
+
+
+def np_float_str(v) -> str:
+    """str(numpy.float32(v)) as the native BOX writer prints it (test hook)."""
+    b = C.create_string_buffer(64)
+    n = lib.rgc_np_float_str(C.c_float(float(v)), b, 64)
+    if n < 0:
+        raise RGCError("rgc_np_float_str failed")
+    return b.value.decode()
 
 
 class Result:

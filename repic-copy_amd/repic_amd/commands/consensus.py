@@ -1,0 +1,219 @@
+"""``repic consensus`` — picker BOX directories to the final consensus ``.box`` files in one
+device pass.
+
+The reference workflow is always ``get_cliques`` followed at once by ``run_ilp`` (run.sh):
+the four pickles and the TSV ``get_cliques`` writes per micrograph exist only so that
+``run_ilp`` can read them again.  This command does both halves on the device without the
+files in between (``rgc_consensus``, ABI 10): the per-clique arrays (rows, weights,
+confidences, consensus ids) stay in HBM from the clique kernels through the set-packing solver,
+and only the picked particles come back.
+
+Same plugin protocol (``name``, ``add_arguments``, ``main``).  The front half is
+``get_cliques``' own, by import: the ``MAX_K`` check before anything is deleted, the ``out_dir``
+reset, ``DirIndex``, ``probe_start_method``, ``plan_chunk`` on a parser thread that overlaps the
+device, ``split_batches``.  Outputs in ``out_dir``: one ``<base>.box`` per micrograph, byte for
+byte what ``get_cliques`` + ``run_ilp`` write (empty for a skipped micrograph), and one
+``consensus_summary.tsv`` for the run.  No pickles, no ``_runtime.tsv``, no per-micrograph
+status files.
+
+Failure semantics are the two-step path's: at the first micrograph where ``get_cliques`` would
+raise (parse crash, no edges -> ValueError, no cliques -> UnboundLocalError) every earlier
+micrograph's ``.box`` exists and the same exception class is raised; an ok micrograph whose
+packing is empty raises ``run_ilp``'s AssertionError; NODE_LIMIT / HEURISTIC micrographs get
+``run_ilp``'s warnings on stderr.  There is no ``--multi_out`` (the reference's ``run_ilp``
+raises on such inputs) and no multi-rank form yet: with ``WORLD_SIZE > 1`` the command raises
+before it creates a device context or touches ``out_dir``.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+from .. import _lib, ilp
+from ..pipeline import split_batches
+from ..writers import BoxWriter
+from . import get_cliques as gc
+from .run_ilp import STATUS_NAMES
+
+name = "consensus"
+
+SUMMARY = "consensus_summary.tsv"
+SUMMARY_HEADER = "base\tstatus\tcliques\tpicks\tcc_max\tcc_cnt\tilp_status\trel_gap\n"
+
+# phase seconds, counts and the library's host<->device byte counts of the last run in this
+# process (tools/consensus_bench.py reads them)
+LAST_RUN: dict = {}
+
+
+def add_arguments(parser):
+    parser.add_argument("in_dir",
+                        help="path to input directory containing subdirectories of particle coordinate files ")
+    parser.add_argument("out_dir",
+                        help="path to output directory (WARNING - script will delete directory if it exists)")
+    parser.add_argument("box_size", type=int,
+                        help="particle detection box size (in int[pixels])")
+    parser.add_argument("--num_particles", type=int,
+                        help="filter for the number of expected particles (int)")
+    parser.add_argument("--get_cc", action="store_true",
+                        help="filters cliques for those in the largest Connected Component (CC)")
+    parser.add_argument("--node_limit", type=int, default=0,
+                        help="branch-and-bound nodes per conflict component (0: the library "
+                             "default), as for run_ilp")
+    parser.add_argument("--batch_boxes", type=int, default=1 << 25,
+                        help="max boxes per device batch (does not change outputs)")
+    parser.add_argument("--threads", type=int, default=None,
+                        help="host BOX-parser threads (does not change outputs)")
+    parser.add_argument("--device", type=int, default=None,
+                        help="HIP device (default: $LOCAL_RANK or 0)")
+    parser.add_argument("--listing", type=gc._load_listing, default=None, help=argparse.SUPPRESS)
+
+
+def main(args):
+    assert os.path.exists(args.in_dir), "Error - input directory does not exist"
+    world, rank, local = gc._dist_env()
+    if world > 1:
+        raise _lib.RGCError(
+            f"repic consensus runs on one rank (WORLD_SIZE={world}): the sharded form needs "
+            "the box-id exchange of get_cliques' multi-rank path and is not built yet; run "
+            "get_cliques and run_ilp under torchrun instead (nothing was deleted or written)")
+    args.multi_out = False
+    dev = args.device if getattr(args, "device", None) is not None else local
+    ctx = _lib.Context(dev)
+    runs = []
+
+    def run_cls(*a):
+        runs.append(_Run(*a))
+        return runs[-1]
+    t0 = time.time()
+    try:
+        gc._main(args, ctx, 1, 0, run_cls=run_cls,
+                 make_writer=lambda a: BoxWriter(getattr(a, "threads", None)))
+    finally:
+        ctx.close()
+        LAST_RUN.clear()
+        LAST_RUN.update(gc.LAST_RUN)
+        LAST_RUN["total_s"] = time.time() - t0
+        if runs and os.path.isdir(args.out_dir):
+            with open(os.path.join(args.out_dir, SUMMARY), "wt") as o:
+                o.write(SUMMARY_HEADER)
+                o.writelines(runs[0].summary)
+
+
+class _Res:
+    """Flat host results of a chunk: per-micrograph arrays and the pick arrays (copies)."""
+
+    PER_MG = ("status", "cc_max", "cc_cnt", "n_vert", "n_edges_mg", "clique_cnt", "sel_cnt",
+              "ilp_status", "ilp_gap")
+
+    def __init__(self, r):
+        for f in ("status", "cc_max", "cc_cnt", "n_vert", "n_edges_mg", "clique_cnt"):
+            setattr(self, f, np.array(getattr(r.run, f)))
+        self.sel_cnt, self.ilp_status, self.ilp_gap = r.sel_cnt, r.ilp_status, r.ilp_gap
+        self.pick_off = r.pick_off
+        self.px, self.py, self.pconf = r.px, r.py, r.pconf
+
+    def append(self, o):
+        for f in self.PER_MG:
+            setattr(self, f, np.concatenate([getattr(self, f), getattr(o, f)]))
+        self.pick_off = np.concatenate([self.pick_off, o.pick_off[1:] + self.pick_off[-1]])
+        self.px = np.concatenate([self.px, o.px])
+        self.py = np.concatenate([self.py, o.py])
+        self.pconf = np.concatenate([self.pconf, o.pconf])
+        return self
+
+
+class _Run(gc._Run):
+    """get_cliques' chunk pipeline with the device stage replaced by ``Context.consensus`` and
+    the write stage by the BOX writer."""
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        self.stats.update(picks=0, h2d_bytes=0, d2h_bytes=0)
+        self.summary = []
+        self._empty = None
+
+    def device(self, ch):
+        ch.res = None
+        if ch.batch is None:
+            return
+        t0 = time.time()
+        b = ch.batch
+        flags = 0
+        if getattr(self.args, "no_fused", False):
+            flags |= _lib.F_NO_FUSED
+        if self.args.get_cc:
+            flags |= _lib.F_GET_CC
+        for m0, m1 in split_batches(np.diff(b.box_off[::self.k]).tolist(),
+                                    getattr(self.args, "batch_boxes", 1 << 25)):
+            part = b if (m0 == 0 and m1 == b.n_mg) else b.slice(m0, m1)
+            r = self.ctx.consensus(part.n_mg, part.k, part.box_size, part.box_off, part.id_base,
+                                   part.x, part.y, part.score, flags,
+                                   node_limit=getattr(self.args, "node_limit", 0) or 0,
+                                   num_particles=self.args.num_particles)
+            self.stats["h2d_bytes"] += r.h2d_bytes
+            self.stats["d2h_bytes"] += r.d2h_bytes
+            ch.res = _Res(r) if ch.res is None else ch.res.append(_Res(r))
+        self.stats["device_s"] += time.time() - t0
+        ok = ch.res.status == _lib.OK
+        self.stats["edges"] += int(ch.res.n_edges_mg[ok].sum())
+        self.stats["cliques"] += int(ch.res.clique_cnt[ok].sum())
+
+    def write(self, ch, writer, stop=None):
+        mgs = ch.mgs if stop is None else ch.mgs[:stop]
+        t0 = time.time()
+        r = ch.res
+        bases, offs, counts = [], [], []
+        raise_at = None
+
+        def flush():
+            if bases:
+                writer.boxes(self.args.out_dir, list(bases), self.args.box_size, list(offs),
+                             list(counts), r.px if r is not None else None,
+                             r.py if r is not None else None,
+                             r.pconf if r is not None else None)
+                bases.clear(), offs.clear(), counts.clear()
+        for mg in mgs:
+            print(f"\n--- {mg.base} ---\n")
+            if mg.status == "skip":
+                print("Skipping micrograph - not all methods have picked particles...")
+                bases.append(mg.base), offs.append(0), counts.append(-1)
+                self.summary.append(f"{mg.base}\tskip\t0\t0\t0\t0\t-\t-\n")
+            elif mg.status == "crash" or r.status[mg.slot] != _lib.OK:
+                raise_at = mg
+                break
+            else:
+                s = mg.slot
+                st = int(r.ilp_status[s])
+                if st == ilp.NODE_LIMIT:
+                    print(f"Warning - {mg.base}: node limit reached in a conflict component and "
+                          f"its Lagrangian bound leaves a gap above 1e-4: the packing is the "
+                          f"best found, not proven optimal", file=sys.stderr)
+                elif st == ilp.HEURISTIC:
+                    print(f"Warning - {mg.base}: a conflict component of more than "
+                          f"{_lib.ilp_big_max()} cliques was not searched; the packing is greedy "
+                          f"+ swap local search and its Lagrangian bound leaves a gap above 1e-4",
+                          file=sys.stderr)
+                if r.sel_cnt[s] < 1:      # run_ilp.py:66-69: at least one clique chosen
+                    raise_at = self._empty = mg
+                    break
+                n = int(r.pick_off[s + 1] - r.pick_off[s])
+                bases.append(mg.base), offs.append(int(r.pick_off[s])), counts.append(n)
+                self.summary.append(
+                    f"{mg.base}\tok\t{int(r.clique_cnt[s])}\t{n}\t{int(r.cc_max[s])}\t"
+                    f"{int(r.cc_cnt[s])}\t{STATUS_NAMES[st]}\t{float(r.ilp_gap[s]):.3e}\n")
+                self.stats["micrographs"] += 1
+                self.stats["picks"] += n
+            if len(bases) >= gc.GROUP_MG:
+                flush()
+        flush()
+        self.stats["write_s"] += time.time() - t0
+        return raise_at
+
+    def raise_for(self, mg, ch):
+        if mg is self._empty:
+            raise AssertionError("Error - vertices are assigned to multiple cliques")
+        gc._Run.raise_for(mg, ch)

@@ -117,7 +117,9 @@ def _shard_weights(in_dir, methods, index, names):
     return 1.0 + s * s * (k * (k - 1) / 2.0)
 
 
-def _main(args, ctx, world, rank):
+def _main(args, ctx, world, rank, run_cls=None, make_writer=None):
+    """``run_cls`` / ``make_writer``: the per-chunk stages and the writer of another command
+    that shares this front half (commands/consensus.py); get_cliques itself passes neither."""
     t_start = time.time()
     dist = None
     if world > 1:
@@ -147,7 +149,7 @@ def _main(args, ctx, world, rank):
     if dist is not None:
         b = shard_bounds(_shard_weights(args.in_dir, methods, index, names), world)
         lo, hi = b[rank], b[rank + 1]
-    run = _Run(args, ctx, methods, index, names[lo:hi], lo)
+    run = (run_cls or _Run)(args, ctx, methods, index, names[lo:hi], lo)
     # optimistic sharded writes need distinct output names: a failure's cleanup must never
     # remove a file an earlier micrograph of another shard also wrote
     run.unique_bases = len({n.replace(".box", "") for n in names}) == len(names)
@@ -155,8 +157,9 @@ def _main(args, ctx, world, rank):
     try:
         # large runs write from spawned processes, started now so they import during the
         # parse and the device work
-        writer = Writer(getattr(args, "threads", None),
-                        processes=len(names) >= PROC_WRITER_MIN * max(1, world))
+        writer = (make_writer(args) if make_writer is not None else
+                  Writer(getattr(args, "threads", None),
+                         processes=len(names) >= PROC_WRITER_MIN * max(1, world)))
         if dist is None:
             run.stream(writer)
         else:

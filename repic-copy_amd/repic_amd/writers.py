@@ -21,7 +21,6 @@ import pickle
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
-from scipy.sparse import coo_matrix
 
 LABELS = ("weight_vector", "consensus_coords", "consensus_confidences", "constraint_matrix")
 # coo_matrix.__dict__ keys the native writer emits (scipy >= 1.13 layout)
@@ -36,6 +35,8 @@ def write_skip(out_dir: str, base: str):
 
 def constraint_matrix(rows: np.ndarray, n_vert: int):
     """coo_matrix(([1]*nnz, (rows, cols)), shape=(V, C)) with cols = [j]*k (:192-202)."""
+    # (imported here: `repic consensus` writes no pickles and does not pay for scipy's import)
+    from scipy.sparse import coo_matrix
     C, k = rows.shape
     cols = np.repeat(np.arange(C, dtype=np.int32), k)
     data = np.ones(C * k, dtype=np.int64)
@@ -246,6 +247,54 @@ def write_group(out_dir, items, w, conf, rows, cx, cy, cid):
 SKIP_FILES = (".box",)
 OK_FILES = ("_weight_vector.pickle", "_consensus_coords.pickle",
             "_consensus_confidences.pickle", "_constraint_matrix.pickle", "_runtime.tsv")
+
+
+class BoxWriter:
+    """Pooled writer of ``repic consensus``: groups of final ``<base>.box`` files through the
+    library's ``rgc_write_boxes`` (C++ formatting and file creation without the GIL) on a few
+    threads.  ``close()`` waits for every pending write and re-raises the first I/O error, so
+    the files of every micrograph before a crash exist."""
+
+    def __init__(self, threads=None):
+        n = threads or min(16, (os.cpu_count() or 1))
+        # (file creation in one directory serialises on its inode lock, as for Writer)
+        self.threads = max(1, min(n, int(os.environ.get("RGC_WRITER_THREADS", 4))))
+        self._pool = ThreadPoolExecutor(max_workers=self.threads) if self.threads > 1 else None
+        self._futs = []
+        self._bases = set()
+        self.written = []
+
+    def boxes(self, out_dir, bases, box_size, pick_off, count, px, py, pconf):
+        """One task: ``<base>.box`` of each micrograph, picks ``pick_off[m] : + count[m]`` of
+        the pick arrays (count -1: the empty file of a skipped micrograph)."""
+        from . import _lib
+        if any(b in self._bases for b in bases):   # same name twice: the reference's order
+            self._drain()
+        self._bases.update(bases)
+        self.written.extend((b, SKIP_FILES) for b in bases)
+        if px is None:
+            px = py = np.zeros(0, np.float64)
+            pconf = np.zeros(0, np.float32)
+        args = (out_dir, bases, box_size, pick_off, count, px, py, pconf)
+        if self._pool is None:
+            _lib.write_boxes(*args)
+            return
+        self._futs.append(self._pool.submit(_lib.write_boxes, *args))
+        if len(self._futs) > 4 * self.threads:
+            self._drain(len(self._futs) // 2)
+
+    def _drain(self, n=None):
+        n = len(self._futs) if n is None else n
+        done, self._futs = self._futs[:n], self._futs[n:]
+        for f in done:
+            f.result()
+
+    def close(self):
+        try:
+            self._drain()
+        finally:
+            if self._pool is not None:
+                self._pool.shutdown(wait=True)
 
 
 class Writer:

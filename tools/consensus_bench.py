@@ -1,0 +1,160 @@
+#!/usr/bin/env python3
+"""File-to-file time of ``repic consensus`` against the two-step path it replaces
+(``repic get_cliques`` then ``repic run_ilp``): BOX directories in, final ``.box`` files out.
+
+  python tools/consensus_bench.py [--config C2] [--n_mg 2000] [--repeats 3]
+                                  [--baseline-root DIR] [--workdir DIR] [--timeout S]
+
+Writes a synthetic BOX directory (``synth.write_box_dirs``, not timed), then ``--repeats``
+times, interleaved, (a) get_cliques + run_ilp and (b) consensus, each into a fresh output
+directory.  This driver never opens the GPU: every command runs in a fresh child process under
+its own ``timeout -k 10``, one at a time, and the chain stops at the first non-zero exit.
+A run's time is the wall time of its child processes (interpreter start and imports included:
+what a user of the CLI waits for).  The ``.box`` files of (a) and (b) must be byte-identical.
+``--baseline-root`` runs (a) from another checkout (e.g. the parent commit, built there).
+Prints one JSON line.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _child(a):
+    """One command in this (fresh) process; phases of the run go to --result as JSON."""
+    sys.path.insert(0, os.path.join(a.root, "repic-copy_amd"))
+    import importlib
+    t0 = time.perf_counter()
+    mod = importlib.import_module(f"repic_amd.commands.{a.child}")
+    t_imp = time.perf_counter() - t0
+    if a.child == "run_ilp":
+        ns = argparse.Namespace(in_dir=a.out_dir, box_size=a.box, num_particles=None,
+                                node_limit=0, device=None)
+    else:
+        ns = argparse.Namespace(in_dir=a.in_dir, out_dir=a.out_dir, box_size=a.box,
+                                multi_out=False, get_cc=False, batch_boxes=1 << 25, threads=None,
+                                device=None, listing=None, num_particles=None, node_limit=0)
+    with open(os.devnull, "w") as null:
+        so, sys.stdout = sys.stdout, null     # the per-micrograph banner lines
+        try:
+            mod.main(ns)
+        finally:
+            sys.stdout = so
+    res = {"import_s": t_imp, "main_s": time.perf_counter() - t0 - t_imp}
+    last = getattr(mod, "LAST_RUN", None)
+    if last:
+        res.update({k: v for k, v in last.items() if isinstance(v, (int, float))})
+    with open(a.result, "w") as f:
+        json.dump(res, f)
+
+
+def _run_child(cmd, root, in_dir, out_dir, box, limit, work):
+    """-> (wall seconds, the child's phase dict); raises on a non-zero exit."""
+    result = os.path.join(work, f"res_{cmd}.json")
+    if os.path.exists(result):
+        os.remove(result)
+    argv = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__),
+            "--child", cmd, "--root", root, "--in_dir", in_dir, "--out_dir", out_dir,
+            "--box", str(box), "--result", result]
+    t0 = time.perf_counter()
+    r = subprocess.run(argv, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
+    wall = time.perf_counter() - t0
+    if r.returncode != 0:
+        raise SystemExit(f"consensus_bench: `{cmd}` from {root} exited {r.returncode} after "
+                         f"{wall:.1f} s; stopping\n{r.stderr[-2000:]}")
+    with open(result) as f:
+        return wall, json.load(f)
+
+
+def _boxes(d):
+    out = {}
+    for e in os.scandir(d):
+        if e.name.endswith(".box"):
+            with open(e.path, "rb") as f:
+                out[e.name] = f.read()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="C2", help="synth.CONFIGS name (C2, C4, ...)")
+    ap.add_argument("--n_mg", type=int, default=2000)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--baseline-root", default=None,
+                    help="checkout whose get_cliques / run_ilp are the two-step path")
+    ap.add_argument("--workdir", default=None)
+    ap.add_argument("--timeout", type=int, default=240, help="seconds per child process")
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    for n in ("--root", "--in_dir", "--out_dir", "--result"):
+        ap.add_argument(n, default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--box", type=int, default=0, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        return _child(a)
+
+    sys.path.insert(0, os.path.join(ROOT, "repic-copy_amd"))
+    from repic_amd import synth
+    cfg = synth.SynthConfig(**synth.CONFIGS[a.config], seed=0)
+    base_root = os.path.abspath(a.baseline_root) if a.baseline_root else ROOT
+    work = tempfile.mkdtemp(prefix="rgc_cons_", dir=a.workdir)
+    out = {"metric": "file-to-file seconds, BOX directories -> final .box files (1 GPU)",
+           "config": a.config, "n_mg": a.n_mg, "k": cfg.k, "repeats": a.repeats,
+           "baseline": "other checkout" if a.baseline_root else "this checkout"}
+    try:
+        in_dir = os.path.join(work, "in")
+        synth.write_box_dirs(in_dir, cfg, a.n_mg)
+        two, one, ph_gc, ph_ilp, ph_c = [], [], [], [], []
+        for i in range(a.repeats):
+            d2, d1 = os.path.join(work, f"two_{i}"), os.path.join(work, f"one_{i}")
+            t_gc, p_gc = _run_child("get_cliques", base_root, in_dir, d2, cfg.box, a.timeout, work)
+            t_il, p_il = _run_child("run_ilp", base_root, in_dir, d2, cfg.box, a.timeout, work)
+            t_c, p_c = _run_child("consensus", ROOT, in_dir, d1, cfg.box, a.timeout, work)
+            two.append(t_gc + t_il)
+            one.append(t_c)
+            ph_gc.append(dict(p_gc, wall_s=t_gc))
+            ph_ilp.append(dict(p_il, wall_s=t_il))
+            ph_c.append(dict(p_c, wall_s=t_c))
+            want, got = _boxes(d2), _boxes(d1)
+            assert sorted(want) == sorted(got), "consensus wrote another set of .box files"
+            bad = [n for n in want if want[n] != got[n]]
+            assert not bad, f".box files differ: {bad[:5]}"
+            out["files_two_step"] = len(os.listdir(d2))
+            out["files_consensus"] = len(os.listdir(d1))
+            out["box_files"] = len(want)
+            shutil.rmtree(d2)
+            shutil.rmtree(d1)
+        out["box_files_identical"] = True
+
+        def med(rows, key):
+            v = [r[key] for r in rows if key in r]
+            return statistics.median(v) if v else None
+        out["two_step_s"] = two
+        out["consensus_s"] = one
+        out["two_step_median_s"] = statistics.median(two)
+        out["consensus_median_s"] = statistics.median(one)
+        out["speedup_median"] = out["two_step_median_s"] / out["consensus_median_s"]
+        out["slowest_consensus_faster_than_fastest_two_step"] = max(one) < min(two)
+        keys = ("wall_s", "import_s", "main_s", "index_s", "parse_s", "device_s", "write_s",
+                "write_tail_s")
+        out["phases_get_cliques"] = {k: med(ph_gc, k) for k in keys if med(ph_gc, k) is not None}
+        out["phases_run_ilp"] = {k: med(ph_ilp, k) for k in keys if med(ph_ilp, k) is not None}
+        out["phases_consensus"] = {k: med(ph_c, k) for k in keys if med(ph_c, k) is not None}
+        c = ph_c[-1]
+        out["cliques"], out["picks"] = c.get("cliques"), c.get("picks")
+        out["h2d_bytes"], out["d2h_bytes"] = c.get("h2d_bytes"), c.get("d2h_bytes")
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
