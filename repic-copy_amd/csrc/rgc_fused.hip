@@ -883,8 +883,10 @@ __device__ __forceinline__ void stencil_setup(Stencil& st, int ts, const FShared
   st.cx = 0;
   st.y0 = 0;
   st.y1 = -1;
-  if (key >= H.nkey) return;
   const int gy = H.gy, nc = H.ncell;
+  // (a box of the last picker has no higher picker to search: no candidates either, and its
+  // waves skip the decode)
+  if (key >= (K - 1) * nc) return;
   // key / ncell and cell / gy through float reciprocals, corrected to the exact quotients
   int p = 0;
 #pragma unroll
@@ -895,22 +897,81 @@ __device__ __forceinline__ void stencil_setup(Stencil& st, int ts, const FShared
   cx -= (cx * gy > cell) ? 1 : 0;
   const int cy = cell - cx * gy;
   // half-column test in f32 (0.0014 columns of slack, see P1): left half -> columns cx-1, cx
-  const float u = (float)(st.a.x - H.minx) * H.inv_cellf;   // = box_key's product on !W
+  // box_key's product: on !W the f32 difference of the two exact f32 values (what the f64
+  // difference rounds to), without the f64 subtraction
+  const float u = (W ? (float)(st.a.x - H.minx) : (float)st.a.x - (float)H.minx) * H.inv_cellf;
   st.p = p;
   st.cx = cx - ((u - (float)cx) < 0.5f ? 1 : 0);
   st.y0 = max(cy - 1, 0);
   st.y1 = min(cy + 1, gy - 1);
 }
 
-// column range [lo, hi) of the stencil in picker q's grid, column st.cx + d (d = 0, 1)
-__device__ __forceinline__ void stencil_range(const Stencil& st, const FShared& S,
-                                              const GridU& H, int q, int d, int& lo, int& hi) {
-  const int col = st.cx + d;
-  lo = hi = 0;
-  if (col < 0 || col >= H.gx) return;
-  const int cb = q * H.ncell + col * H.gy;
-  lo = S.cstart[cb + st.y0];
-  hi = S.cstart[cb + st.y1 + 1];
+// The stencil in picker q's grid as ONE candidate sequence: the position ranges [lo, hi) of its
+// two columns st.cx + d (d = 0, 1) joined, so that a box walks a grid in one loop (a wave pays
+// the longest lane of the sum, not of each range).  Candidate j (0 <= j < n, stencil order:
+// column d = 0, then d = 1, by position) is the box at position j + (j < n0 ? o0 : o1).
+struct Span {
+  int n0, n, o0, o1;
+  __device__ __forceinline__ int at(int j) const { return j + (j < n0 ? o0 : o1); }
+};
+
+// Position bounds {lo0, hi0, lo1, hi1} of the stencil's two columns in picker q's grid (q < K).
+// st.cx lies in [-1, gx - 1]: only the first column can fall left of the grid and only the
+// second right of it; such a column reads cell 0 for both of its bounds (empty).  Nothing is
+// selected after a load, so the loads of a box's spans are in flight together.
+__device__ __forceinline__ void stencil_bounds(const Stencil& st, const FShared& S,
+                                               const GridU& H, int q, int (&b)[4]) {
+  const int cb = q * H.ncell + st.cx * H.gy;
+  const bool ok0 = st.cx >= 0, ok1 = st.cx + 1 < H.gx;
+  b[0] = S.cstart[ok0 ? cb + st.y0 : 0];
+  b[1] = S.cstart[ok0 ? cb + st.y1 + 1 : 0];
+  b[2] = S.cstart[ok1 ? cb + H.gy + st.y0 : 0];
+  b[3] = S.cstart[ok1 ? cb + H.gy + st.y1 + 1 : 0];
+}
+__device__ __forceinline__ Span span_of(const int (&b)[4]) {
+  Span g;
+  g.n0 = b[1] - b[0];
+  g.n = g.n0 + (b[3] - b[2]);
+  g.o0 = b[0];
+  g.o1 = b[2] - g.n0;
+  return g;
+}
+
+// The spans of a K = 3 box's (at most two) target grids, all bounds read before any is used.
+// Lanes of a wave hold neighbouring boxes of one picker, so the waves of picker 2 skip both
+// reads and those of picker 1 the second.
+__device__ __forceinline__ void stencil_spans3(const Stencil& st, const FShared& S,
+                                               const GridU& H, Span& g0, Span& g1) {
+  int b0[4] = {0, 0, 0, 0}, b1[4] = {0, 0, 0, 0};
+  if (st.p + 1 < 3) stencil_bounds(st, S, H, st.p + 1, b0);
+  if (st.p + 2 < 3) stencil_bounds(st, S, H, st.p + 2, b1);
+  g0 = span_of(b0);
+  g1 = span_of(b1);
+}
+
+// P2 walk of a box's candidates in stencil order (picker, column, position): body(t, kk) with
+// the candidate's position t and its ordinal kk.  One flattened loop per target grid (not
+// unrolled: a grid's stencil holds a few candidates).
+template <int K, typename F>
+__device__ __forceinline__ void stencil_walk(const Stencil& st, const FShared& S,
+                                             const GridU& H, F&& body) {
+  int kk = 0;
+  if constexpr (K == 3) {
+    Span g0, g1;
+    stencil_spans3(st, S, H, g0, g1);
+#pragma unroll 1
+    for (int j = 0; j < g0.n; ++j, ++kk) body(g0.at(j), kk);
+#pragma unroll 1
+    for (int j = 0; j < g1.n; ++j, ++kk) body(g1.at(j), kk);
+  } else {
+    for (int q = st.p + 1; q < K; ++q) {
+      int b[4];
+      stencil_bounds(st, S, H, q, b);
+      const Span g = span_of(b);
+#pragma unroll 1
+      for (int j = 0; j < g.n; ++j, ++kk) body(g.at(j), kk);
+    }
+  }
 }
 
 // v_min_f64 / v_max_f64 without the sNaN canonicalisation fmin/fmax carry: grid candidates
@@ -971,37 +1032,29 @@ __device__ __forceinline__ int pairs_count(const Stencil& st, const FShared& S, 
                                            double B, double two_b2, double i_lo, double i_hi,
                                            uint32_t* mask_out, uint32_t* first_out) {
   uint32_t mask = 0, pk = 0, first = 0;
-  int cnt = 0, kk = 0;
+  int cnt = 0;
   // f32 layout: reject in f32 first.  An edge needs both overlaps > (6/13) B, i.e. |dx| and
   // |dy| < (7/13) B = 0.5385 B; the f32 difference of two exact f32 values is within 2^-24 of
   // the true one, so |dx| >= 0.54 B (as computed) can never be an edge.
   const float rej = 0.54f * (float)B;
   const float ax = (float)st.a.x, ay = (float)st.a.y;
-  for (int q = st.p + 1; q < K; ++q) {
-#pragma unroll
-    for (int d = 0; d <= 1; ++d) {
-      int lo, hi;
-      stencil_range(st, S, H, q, d, lo, hi);
-      for (int t = lo; t < hi; ++t, ++kk) {
-        bool e;
-        if constexpr (W) {
-          e = edge_test(st.a, ld_xy<W>(S, t), B, two_b2, i_lo, i_hi);
-        } else {
-          const float2 bf = reinterpret_cast<const float2*>(S.sxy)[t];
-          e = false;
-          if (fabsf(ax - bf.x) < rej && fabsf(ay - bf.y) < rej)
-            e = edge_test(st.a, make_double2((double)bf.x, (double)bf.y), B, two_b2, i_lo,
-                          i_hi);
-        }
-        if (e) {
-          first = cnt == 0 ? (uint32_t)t : first;
-          ++cnt;
-          mask |= (kk < 32) ? (1u << kk) : 0u;
-          pk = (pk << 16) | (uint32_t)t;
-        }
-      }
+  stencil_walk<K>(st, S, H, [&](int t, int kk) {
+    bool e;
+    if constexpr (W) {
+      e = edge_test(st.a, ld_xy<W>(S, t), B, two_b2, i_lo, i_hi);
+    } else {
+      const float2 bf = reinterpret_cast<const float2*>(S.sxy)[t];
+      e = false;
+      if (fabsf(ax - bf.x) < rej && fabsf(ay - bf.y) < rej)
+        e = edge_test(st.a, make_double2((double)bf.x, (double)bf.y), B, two_b2, i_lo, i_hi);
     }
-  }
+    if (e) {
+      first = cnt == 0 ? (uint32_t)t : first;
+      ++cnt;
+      mask |= (kk < 32) ? (1u << kk) : 0u;
+      pk = (pk << 16) | (uint32_t)t;
+    }
+  });
   *mask_out = cnt <= FILL_FAST ? pk : mask;
   *first_out = first;
   return cnt;
@@ -1013,62 +1066,71 @@ __device__ __forceinline__ int pairs_count_int(const Stencil& st, const FShared&
                                                const GridU& H, float Bf, float Tf,
                                                uint32_t* mask_out, uint32_t* first_out) {
   uint32_t mask = 0, pk = 0, first = 0;
-  int cnt = 0, kk = 0;
+  int cnt = 0;
   const float ax = (float)st.a.x, ay = (float)st.a.y;
-  for (int q = st.p + 1; q < K; ++q) {
-#pragma unroll
-    for (int d = 0; d <= 1; ++d) {
-      int lo, hi;
-      stencil_range(st, S, H, q, d, lo, hi);
-      for (int t = lo; t < hi; ++t, ++kk) {
-        const float2 bf = reinterpret_cast<const float2*>(S.sxy)[t];
-        const float xo = fmaxf(Bf - fabsf(ax - bf.x), 0.0f);
-        const float yo = fmaxf(Bf - fabsf(ay - bf.y), 0.0f);
-        if (xo * yo > Tf) {
-          first = cnt == 0 ? (uint32_t)t : first;
-          ++cnt;
-          mask |= (kk < 32) ? (1u << kk) : 0u;
-          pk = (pk << 16) | (uint32_t)t;
-        }
-      }
+  stencil_walk<K>(st, S, H, [&](int t, int kk) {
+    const float2 bf = reinterpret_cast<const float2*>(S.sxy)[t];
+    const float xo = fmaxf(Bf - fabsf(ax - bf.x), 0.0f);
+    const float yo = fmaxf(Bf - fabsf(ay - bf.y), 0.0f);
+    if (xo * yo > Tf) {
+      first = cnt == 0 ? (uint32_t)t : first;
+      ++cnt;
+      mask |= (kk < 32) ? (1u << kk) : 0u;
+      pk = (pk << 16) | (uint32_t)t;
     }
-  }
+  });
   *mask_out = cnt <= FILL_FAST ? pk : mask;
   *first_out = first;
   return cnt;
 }
 
 // P2 fill: write the box's forward targets (positions) at d[0..cnt) from the count's bitmask
-// (re-testing candidates past the 32nd).  Grids are visited in picker order and each grid's
-// column ranges in key order, so the list comes out sorted.
+// (re-testing candidates past the 32nd).  Candidates are visited in stencil_walk's order
+// (picker, column, position), so the list comes out sorted.  K = 3 with at most 32 candidates
+// (every edge has its mask bit): one loop over the set bits of the mask; otherwise one loop
+// per target grid, over the set bits while the grid ends within the mask.
 template <int K, bool W>
 __device__ __forceinline__ void pairs_fill(const Stencil& st, const FShared& S, const GridU& H,
                                            uint32_t mask, uint16_t* d, int cnt, double B,
                                            double two_b2, double i_lo, double i_hi) {
   int c = 0, kk = 0;
-  for (int q = st.p + 1; q < K; ++q) {
-#pragma unroll
-    for (int dd = 0; dd <= 1; ++dd) {
-      int lo, hi;
-      stencil_range(st, S, H, q, dd, lo, hi);
-      const int len = hi - lo;
-      if (kk + len <= 32) {
-        uint32_t bits = kk < 32 ? (mask >> kk) : 0u;
-        bits &= len >= 32 ? ~0u : ((1u << len) - 1u);
-        while (bits) {
-          const int b = __builtin_ctz(bits);
-          bits &= bits - 1;
-          d[c++] = (uint16_t)(lo + b);
-        }
-      } else {
-        for (int t = lo; t < hi; ++t) {
-          const int idx = kk + (t - lo);
-          const bool e = idx < 32 ? ((mask >> idx) & 1u) != 0
-                                  : edge_test(st.a, ld_xy<W>(S, t), B, two_b2, i_lo, i_hi);
-          if (e) d[c++] = (uint16_t)t;
-        }
+  auto fill_grid = [&](const Span& g) {
+    if (kk + g.n <= 32) {
+      uint32_t bits = kk < 32 ? (mask >> kk) : 0u;
+      bits &= g.n >= 32 ? ~0u : ((1u << g.n) - 1u);
+      while (bits) {
+        const int b = __builtin_ctz(bits);
+        bits &= bits - 1;
+        d[c++] = (uint16_t)g.at(b);
       }
-      kk += len;
+    } else {
+      for (int j = 0; j < g.n; ++j) {
+        const int idx = kk + j, t = g.at(j);
+        const bool e = idx < 32 ? ((mask >> idx) & 1u) != 0
+                                : edge_test(st.a, ld_xy<W>(S, t), B, two_b2, i_lo, i_hi);
+        if (e) d[c++] = (uint16_t)t;
+      }
+    }
+    kk += g.n;
+  };
+  if constexpr (K == 3) {
+    Span g0, g1;
+    stencil_spans3(st, S, H, g0, g1);
+    if (g0.n + g1.n <= 32) {
+      while (mask) {
+        const int b = __builtin_ctz(mask);
+        mask &= mask - 1;
+        d[c++] = (uint16_t)(b < g0.n ? g0.at(b) : g1.at(b - g0.n));
+      }
+    } else {
+      fill_grid(g0);
+      fill_grid(g1);
+    }
+  } else {
+    for (int q = st.p + 1; q < K; ++q) {
+      int b[4];
+      stencil_bounds(st, S, H, q, b);
+      fill_grid(span_of(b));
     }
   }
 }
