@@ -15,7 +15,7 @@
 // Phases (barrier-separated), reference repic/commands/get_cliques.py:
 //   P0 load x, y; bounding box
 //   P1 grid + LDS counting sort by cell                       (pair loop structure :62-63)
-//   P2 JI pairs: count -> scan -> fill, sort each list        (:40-46, :59-69, :138)
+//   P2 JI pairs: count and write each sorted list, one pass   (:40-46, :59-69, :138)
 //   P3 union-find, CC stats, --get_cc target                  (:145-156)
 //   P4 k-clique DFS count, mark vertices, reserve outputs    (:49-56, :160-161)
 //   P5 vertex rank by (x, y, id) via x-major grid columns    (:164, :193)
@@ -76,6 +76,7 @@ struct FusedHdr {
   double xbs;       // P5 x-bucket scale: bucket(x) = min(trunc((x - minx) * xbs), n - 1)
   float inv_gy;
   int gx, gy, ncell, nkey;   // per-picker grid gx x gy; keys picker * ncell + cell; nkey = none
+  // E: forward edges; P2's cursor (each wave-round reserves its block's lists on it)
   int E, nodes, cc_cnt, cc_max, target, V, status;
   uint32_t ccur;    // P4 clique-queue cursor
   int tief[2];      // P6: some clique of the chunk needs the order pass (by chunk parity)
@@ -87,6 +88,13 @@ struct FusedHdr {
 // where LDS is the limit (one workgroup per CU) and larger cells only cost P2 candidates
 __host__ __device__ inline int fused_cells(int nmax) { return nmax <= 2048 ? 4 * nmax : 2 * nmax; }
 
+// P2 reserves the lists of one aligned block of 64 positions at a time, in the waves' arrival
+// order, so a box's list ends where the next box's begins only inside a block: fwd holds every
+// box's list begin, and bend (behind fwd's fwd_blocks(nmax) * 64 begins) every block's end, read
+// for the last box of a block only.  A begin costs what it did with one monotone offset array
+// (P4's level expansion reads begins only).
+__host__ __device__ inline int fwd_blocks(int nmax) { return (nmax + 63) / 64; }
+
 // wide: f64 coordinates in LDS; otherwise f32 (every coordinate of the micrograph is exactly
 // representable as f32, checked in P0, so the f64 values are recovered exactly)
 __host__ __device__ inline FusedLayout fused_layout(int nmax, int ecap, bool wide) {
@@ -96,7 +104,8 @@ __host__ __device__ inline FusedLayout fused_layout(int nmax, int ecap, bool wid
   // live until the end of the kernel
   L.off_sxy = o; o += al((wide ? 16 : 8) * nmax);   // (x, y) in cell-sorted order
   L.off_cnt = o; o += al(4 * (nmax + 4));
-  L.off_fwd = o; o += al(2 * (nmax + 4));     // u16 CSR offsets (E <= ecap <= 65535)
+  // u16 list bounds (E <= ecap <= 65535): each box's list begin, then each block's end (bend)
+  L.off_fwd = o; o += al(2 * (fwd_blocks(nmax) * 65 + 4));
   L.off_pos = o; o += al(2 * nmax);           // local box index -> sorted position
   L.off_vrank = o; o += al(2 * nmax);
   L.off_dst = o; o += al(2 * ecap);
@@ -121,6 +130,7 @@ struct FShared {
   uint16_t* cstart;
   uint32_t* cnt;
   uint16_t* fwd;
+  uint16_t* bend;   // end of each block's lists (see fwd_blocks)
   uint16_t* parent;
   uint16_t* citems;
   uint16_t* pos;
@@ -134,6 +144,11 @@ struct FShared {
                     // rank, used when 8 V bytes fit there (vstaged); else scores are
                     // gathered from HBM
   bool vstaged;
+  // forward list of the box at position i: dst[eb(i), ee(i))
+  __device__ __forceinline__ int eb(int i) const { return fwd[i]; }
+  __device__ __forceinline__ int ee(int i) const {
+    return (i & 63) == 63 ? bend[i >> 6] : fwd[i + 1];
+  }
 };
 
 template <bool W>
@@ -357,14 +372,14 @@ __device__ __forceinline__ uint64_t ins_key(const FCtx<K>& c, int u) {
   const int lu = (int)c.S.citems[u] - bu;
   for (int a = 0; a < bu; ++a) {   // lower-picker boxes in file order
     const int ap = c.S.pos[a];
-    if (contains16(c.S.dst, c.S.fwd[ap], c.S.fwd[ap + 1], u)) {
+    if (contains16(c.S.dst, c.S.eb(ap), c.S.ee(ap), u)) {
       const int qa = picker_of<K>(c.pb, a);
       return ((uint64_t)pair_index(qa, pu, K) << 49) |
              ((uint64_t)(a - picker_begin<K>(c.pb, qa)) << 25) | ((uint64_t)lu << 1) | 1ULL;
     }
   }
   // no incoming edge: its first outgoing edge = lowest target picker, smallest file index
-  const int e0 = c.S.fwd[u], e1 = c.S.fwd[u + 1];
+  const int e0 = c.S.eb(u), e1 = c.S.ee(u);
   const int d0 = c.S.dst[e0];
   const int pd = picker_of<K>(c.pp, d0);
   const int se = lb16(c.S.dst, e0, e1, picker_end<K>(c.pp, d0));
@@ -573,16 +588,16 @@ struct FLevel {
     // forward list: [fwd, split) from P3, or by binary search in the P6 re-walk (split's
     // LDS is reused by then)
     const int prev = mem[D - 1];
-    const int lo = c.S.fwd[prev];
+    const int lo = c.S.eb(prev);
     int hi;
-    if (FILL) hi = lb16(c.S.dst, lo, c.S.fwd[prev + 1], c.pp[D + 1]);
+    if (FILL) hi = lb16(c.S.dst, lo, c.S.ee(prev), c.pp[D + 1]);
     else hi = c.S.split[prev];
     for (int e = lo; e < hi; ++e) {
       const int h = c.S.dst[e];
       bool ok = true;
 #pragma unroll
       for (int q = 0; q < D - 1; ++q) {
-        if (!contains16(c.S.dst, c.S.fwd[mem[q]], c.S.fwd[mem[q] + 1], h)) { ok = false; break; }
+        if (!contains16(c.S.dst, c.S.eb(mem[q]), c.S.ee(mem[q]), h)) { ok = false; break; }
       }
       if (!ok) continue;
       mem[D] = h;
@@ -683,7 +698,7 @@ struct BfsLevel {
 
   template <bool REWALK>
   __device__ __forceinline__ static int seg_end(const FShared& S, const int (&pp)[K + 1], int m) {
-    if (REWALK) return lb16(S.dst, S.fwd[m], S.fwd[m + 1], pp[D + 1]);
+    if (REWALK) return lb16(S.dst, S.eb(m), S.ee(m), pp[D + 1]);
     return S.split[m];
   }
 
@@ -710,7 +725,7 @@ struct BfsLevel {
       int mm[K];
       prefix(q, lvl, (uint32_t)e, mm);
       const int m = mm[D - 1];
-      const int lo = S.fwd[m], hi = seg_end<REWALK>(S, pp, m);
+      const int lo = S.eb(m), hi = seg_end<REWALK>(S, pp, m);
       uint32_t mask = 0, cnt = 0;
       // an extension h (picker D) must be adjacent to every earlier member: the graph's edges
       // are exactly the pairs of different pickers with JI > 0.3, so instead of a binary
@@ -750,7 +765,7 @@ struct BfsLevel {
       int mm[K];
       prefix(q, lvl, (uint32_t)e, mm);
       const int m = mm[D - 1];
-      const int lo = S.fwd[m], hi = seg_end<REWALK>(S, pp, m);
+      const int lo = S.eb(m), hi = seg_end<REWALK>(S, pp, m);
       const uint32_t mask = MK[e];
       uint32_t o = CN[e];
       for (int t = lo; t < hi; ++t) {
@@ -811,17 +826,17 @@ __device__ __forceinline__ BfsOut<K> bfs_cliques(const FShared& S, FusedHdr& H, 
   const int nr = r1 - r0;
   auto root_ok = [&](int r) {
     if (REWALK) return S.flags[r] == 3;
-    return S.fwd[r] < S.fwd[r + 1] && (!get_cc || S.parent[r] == target);
+    return S.eb(r) < S.ee(r) && (!get_cc || S.parent[r] == target);
   };
   auto seg_end = [&](int r) {
-    if (REWALK) return lb16(S.dst, S.fwd[r], S.fwd[r + 1], pp[2]);
+    if (REWALK) return lb16(S.dst, S.eb(r), S.ee(r), pp[2]);
     return (int)S.split[r];
   };
   // level 1 -> 2: every root's first segment (picker-1 neighbours), no checks needed
   uint32_t* cnt = S.cnt;
   for (int i = tid; i < nr; i += NT) {
     const int r = r0 + i;
-    cnt[i] = root_ok(r) ? (uint32_t)(seg_end(r) - S.fwd[r]) : 0u;
+    cnt[i] = root_ok(r) ? (uint32_t)(seg_end(r) - S.eb(r)) : 0u;
   }
   __syncthreads();
   const int64_t n2 = ufl(block_scan_dpp32<NT>(cnt, nr, H.redi));   // (< n^2 < 2^31)
@@ -837,7 +852,7 @@ __device__ __forceinline__ BfsOut<K> bfs_cliques(const FShared& S, FusedHdr& H, 
     if (!root_ok(r)) continue;
     uint32_t o = cnt[i];
     const int se = seg_end(r);
-    for (int t = S.fwd[r]; t < se; ++t, ++o) {
+    for (int t = S.eb(r); t < se; ++t, ++o) {
       const int h = S.dst[t];
       if constexpr (WE) reinterpret_cast<uint2*>(q)[o] = make_uint2((uint32_t)r | ((uint32_t)h << 16), 0u);
       else reinterpret_cast<uint32_t*>(q)[o] = ((uint32_t)r << 16) | (uint32_t)h;
@@ -860,9 +875,8 @@ __device__ __forceinline__ BfsOut<K> bfs_cliques(const FShared& S, FusedHdr& H, 
   }
 }
 
-// P2: boxes with up to FILL_FAST forward edges have their targets kept by the count (the
-// last two in cnt, the first of three in the CC-size slot, zero until P3); the fill writes
-// them without walking the stencil again
+// P2: a box with up to FILL_FAST forward edges has its targets packed by the count itself;
+// its list is written from them without walking the edge bitmask
 constexpr int FILL_FAST = 2;
 
 // Candidates of a box: the 2x3 cell stencil at its cell in the grid of every HIGHER picker
@@ -910,9 +924,12 @@ __device__ __forceinline__ void stencil_setup(Stencil& st, int ts, const FShared
 // two columns st.cx + d (d = 0, 1) joined, so that a box walks a grid in one loop (a wave pays
 // the longest lane of the sum, not of each range).  Candidate j (0 <= j < n, stencil order:
 // column d = 0, then d = 1, by position) is the box at position j + (j < n0 ? o0 : o1).
+// (The second column's offset is kept as its difference d to the first's and added under a
+// predicate: a select between two members of a span that is still in memory when the optimiser
+// meets it becomes a dynamically indexed load, which moves the spans to scratch.)
 struct Span {
-  int n0, n, o0, o1;
-  __device__ __forceinline__ int at(int j) const { return j + (j < n0 ? o0 : o1); }
+  int n0, n, o0, d;
+  __device__ __forceinline__ int at(int j) const { return j + o0 + (j >= n0 ? d : 0); }
 };
 
 // Position bounds {lo0, hi0, lo1, hi1} of the stencil's two columns in picker q's grid (q < K).
@@ -933,7 +950,7 @@ __device__ __forceinline__ Span span_of(const int (&b)[4]) {
   g.n0 = b[1] - b[0];
   g.n = g.n0 + (b[3] - b[2]);
   g.o0 = b[0];
-  g.o1 = b[2] - g.n0;
+  g.d = b[2] - g.n0 - b[0];
   return g;
 }
 
@@ -951,13 +968,13 @@ __device__ __forceinline__ void stencil_spans3(const Stencil& st, const FShared&
 
 // P2 walk of a box's candidates in stencil order (picker, column, position): body(t, kk) with
 // the candidate's position t and its ordinal kk.  One flattened loop per target grid (not
-// unrolled: a grid's stencil holds a few candidates).
+// unrolled: a grid's stencil holds a few candidates).  K = 3 leaves its two spans in g0, g1
+// for the list write that follows the count.
 template <int K, typename F>
 __device__ __forceinline__ void stencil_walk(const Stencil& st, const FShared& S,
-                                             const GridU& H, F&& body) {
+                                             const GridU& H, Span& g0, Span& g1, F&& body) {
   int kk = 0;
   if constexpr (K == 3) {
-    Span g0, g1;
     stencil_spans3(st, S, H, g0, g1);
 #pragma unroll 1
     for (int j = 0; j < g0.n; ++j, ++kk) body(g0.at(j), kk);
@@ -1024,21 +1041,21 @@ struct EdgeP {
 };
 
 // P2 count for the box at sorted position ts (thread per box): JI test against every stencil
-// candidate of a higher picker; returns the edge count and, for the fill, either the targets
-// themselves (at most 2 edges: first << 16 | second, ascending) or the bitmask of edge
-// candidates (candidates 0..31 in stencil order; later candidates are re-tested by the fill).
+// candidate of a higher picker; returns the edge count and, for the list write, either the
+// targets themselves (at most 2 edges: first << 16 | second, ascending) or the bitmask of edge
+// candidates (candidates 0..31 in stencil order; later candidates are re-tested by the write).
 template <int K, bool W>
 __device__ __forceinline__ int pairs_count(const Stencil& st, const FShared& S, const GridU& H,
                                            double B, double two_b2, double i_lo, double i_hi,
-                                           uint32_t* mask_out, uint32_t* first_out) {
-  uint32_t mask = 0, pk = 0, first = 0;
+                                           Span& g0, Span& g1, uint32_t* mask_out) {
+  uint32_t mask = 0, pk = 0;
   int cnt = 0;
   // f32 layout: reject in f32 first.  An edge needs both overlaps > (6/13) B, i.e. |dx| and
   // |dy| < (7/13) B = 0.5385 B; the f32 difference of two exact f32 values is within 2^-24 of
   // the true one, so |dx| >= 0.54 B (as computed) can never be an edge.
   const float rej = 0.54f * (float)B;
   const float ax = (float)st.a.x, ay = (float)st.a.y;
-  stencil_walk<K>(st, S, H, [&](int t, int kk) {
+  stencil_walk<K>(st, S, H, g0, g1, [&](int t, int kk) {
     bool e;
     if constexpr (W) {
       e = edge_test(st.a, ld_xy<W>(S, t), B, two_b2, i_lo, i_hi);
@@ -1049,50 +1066,48 @@ __device__ __forceinline__ int pairs_count(const Stencil& st, const FShared& S, 
         e = edge_test(st.a, make_double2((double)bf.x, (double)bf.y), B, two_b2, i_lo, i_hi);
     }
     if (e) {
-      first = cnt == 0 ? (uint32_t)t : first;
       ++cnt;
       mask |= (kk < 32) ? (1u << kk) : 0u;
       pk = (pk << 16) | (uint32_t)t;
     }
   });
   *mask_out = cnt <= FILL_FAST ? pk : mask;
-  *first_out = first;
   return cnt;
 }
 
 // P2 count on integer coordinates (f32 layout, see P2): exact f32 overlaps, I > floor(6B^2/13)
 template <int K>
 __device__ __forceinline__ int pairs_count_int(const Stencil& st, const FShared& S,
-                                               const GridU& H, float Bf, float Tf,
-                                               uint32_t* mask_out, uint32_t* first_out) {
-  uint32_t mask = 0, pk = 0, first = 0;
+                                               const GridU& H, float Bf, float Tf, Span& g0,
+                                               Span& g1, uint32_t* mask_out) {
+  uint32_t mask = 0, pk = 0;
   int cnt = 0;
   const float ax = (float)st.a.x, ay = (float)st.a.y;
-  stencil_walk<K>(st, S, H, [&](int t, int kk) {
+  stencil_walk<K>(st, S, H, g0, g1, [&](int t, int kk) {
     const float2 bf = reinterpret_cast<const float2*>(S.sxy)[t];
     const float xo = fmaxf(Bf - fabsf(ax - bf.x), 0.0f);
     const float yo = fmaxf(Bf - fabsf(ay - bf.y), 0.0f);
     if (xo * yo > Tf) {
-      first = cnt == 0 ? (uint32_t)t : first;
       ++cnt;
       mask |= (kk < 32) ? (1u << kk) : 0u;
       pk = (pk << 16) | (uint32_t)t;
     }
   });
   *mask_out = cnt <= FILL_FAST ? pk : mask;
-  *first_out = first;
   return cnt;
 }
 
-// P2 fill: write the box's forward targets (positions) at d[0..cnt) from the count's bitmask
-// (re-testing candidates past the 32nd).  Candidates are visited in stencil_walk's order
-// (picker, column, position), so the list comes out sorted.  K = 3 with at most 32 candidates
-// (every edge has its mask bit): one loop over the set bits of the mask; otherwise one loop
-// per target grid, over the set bits while the grid ends within the mask.
+// P2 list write: the box's forward targets (positions) to d[0..) from the count's bitmask
+// (re-testing candidates past the 32nd), right after the count.  Candidates are visited in
+// stencil_walk's order (picker, column, position), so the list comes out sorted.  K = 3 (spans
+// g0, g1 still held from the count) with at most 32 candidates (every edge has its mask bit):
+// one loop over the set bits of the mask; otherwise one loop per target grid (K >= 4 reads the
+// grid's bounds again), over the set bits while the grid ends within the mask.
 template <int K, bool W>
 __device__ __forceinline__ void pairs_fill(const Stencil& st, const FShared& S, const GridU& H,
-                                           uint32_t mask, uint16_t* d, int cnt, double B,
-                                           double two_b2, double i_lo, double i_hi) {
+                                           const Span& g0, const Span& g1, uint32_t mask,
+                                           uint16_t* d, double B, double two_b2, double i_lo,
+                                           double i_hi) {
   int c = 0, kk = 0;
   auto fill_grid = [&](const Span& g) {
     if (kk + g.n <= 32) {
@@ -1114,13 +1129,15 @@ __device__ __forceinline__ void pairs_fill(const Stencil& st, const FShared& S, 
     kk += g.n;
   };
   if constexpr (K == 3) {
-    Span g0, g1;
-    stencil_spans3(st, S, H, g0, g1);
     if (g0.n + g1.n <= 32) {
+      // candidate b of the joined sequence g0, g1: one offset and three predicated steps
+      const int t1 = g0.n, t2 = g0.n + g1.n0;
+      const int d1 = g1.o0 - g0.n - g0.o0 - g0.d;
       while (mask) {
         const int b = __builtin_ctz(mask);
         mask &= mask - 1;
-        d[c++] = (uint16_t)(b < g0.n ? g0.at(b) : g1.at(b - g0.n));
+        d[c++] = (uint16_t)(b + g0.o0 + (b >= g0.n0 ? g0.d : 0) + (b >= t1 ? d1 : 0) +
+                            (b >= t2 ? g1.d : 0));
       }
     } else {
       fill_grid(g0);
@@ -1167,7 +1184,7 @@ __device__ __forceinline__ void put_stats(const FusedArgs& A, int m, int status,
 // waves per SIMD = 4 workgroups per CU, which the f32-coordinate LDS layout also allows; larger
 // K keep the compiler's choice (their VGPRs, not LDS, bound the occupancy).
 constexpr int fused_waves_per_eu(int k, int nt) {
-  return nt == 1024 ? 4 : (nt == 768 ? 6 : (nt == 256 ? 4 : (nt == 384 ? 6 : (k <= 3 ? 8 : 1))));
+  return nt == 1024 ? 4 : (nt == 768 ? 6 : (nt == 256 ? 8 : (nt == 384 ? 6 : (k <= 3 ? 8 : 1))));
 }
 
 // HBM level-tree slots (QG launches): claim a free bit of the slot bitmap (one thread), or -1
@@ -1205,6 +1222,7 @@ void k_fused(FusedArgs A) {
   S.cstart = reinterpret_cast<uint16_t*>(smem + L.off_cstart);
   S.cnt = reinterpret_cast<uint32_t*>(smem + L.off_cnt);
   S.fwd = reinterpret_cast<uint16_t*>(smem + L.off_fwd);
+  S.bend = S.fwd + fwd_blocks(A.nmax) * 64;
   S.split = reinterpret_cast<uint16_t*>(smem + L.off_scell);
   S.vscore = reinterpret_cast<double*>(smem + L.off_parent);
   S.vstaged = false;
@@ -1406,7 +1424,7 @@ void k_fused(FusedArgs A) {
       // -inf minimum: some coordinate is not an integer below 2^23 (P0), the host relaunches
       // the micrograph with the f64 layout
       H.status = (!W && mnx == -INFINITY) ? RGC_ST_DEFER_WIDE : 0;
-      H.C = 0; H.base = 0; H.V = 0; H.target = -1; H.ccur = 0;
+      H.C = 0; H.base = 0; H.V = 0; H.target = -1; H.ccur = 0; H.E = 0;
       H.tief[0] = H.tief[1] = 0;
       H.qslot = 0;
     }
@@ -1460,7 +1478,7 @@ void k_fused(FusedArgs A) {
   STOP_AFTER(1);
   STAMP(2);
   // ---- P2: Jaccard pairs (forward edges to higher pickers): count (JI test, edge bitmask
-  // per box) -> scan -> fill (bitmask replay, no atomics) + per-list sort.
+  // per box) and list write in one pass, lists sorted as written.
   const double B = A.B, two_b2 = A.two_b2;
   // JI > 0.3  <=>  I > (6/13) B^2 exactly; decide without the division unless I lies within a
   // 2^-40 relative band of the threshold, where the reference's f64 quotient is evaluated.
@@ -1477,37 +1495,71 @@ void k_fused(FusedArgs A) {
   const EdgeP<W> ep{(float)B, (float)ti, B, two_b2, i_lo, i_hi};   // (P4's adjacency tests)
   // thread per box (sorted position): lanes of a wave hold neighbouring boxes of one picker,
   // so their stencils overlap (similar trip counts, broadcast LDS reads), and the waves of
-  // picker K-1 have nothing to do.  cnt[] (dead until P3) keeps
-  // each box's targets (<= 2 edges) or edge bitmask for the fill.
+  // picker K-1 have nothing to do.
   uint32_t* ccsz = reinterpret_cast<uint32_t*>(S.vrank);   // packed u16 CC sizes (P2-P3)
+  // One pass per box: a wave-round (one wave, one aligned block of 64 positions) counts its
+  // boxes' edges, scans the counts in position order, reserves the block's lists with one LDS
+  // atomic on the header's edge cursor and writes every list at once from the targets or the
+  // bitmask its lanes still hold (no scan over the workgroup, no second walk of the stencil).
+  // Lists of one block are contiguous in position order; blocks lie in arrival order (fwd / bend).
+  // A wave-round that would pass ecap writes nothing; the cursor still ends at the true total.
+  // The edges' sources for the edge-parallel union are not recorded here: before the total is
+  // known they would have to go to a fixed place in dst, where targets of later wave-rounds
+  // may land as well; the loop after the barrier writes them behind the E targets.
   // boustrophedon box order: odd rounds walk their FWG positions backwards, so a thread that
   // took a low-picker box (most grids to search) in one round takes a high-picker box (fewest)
   // in the next; K = 3, ~900 boxes: at most 6 instead of 9 column ranges per thread
-  for (int r0 = 0, odd = 0; r0 < n; r0 += FWG, odd ^= 1) {
-    const int ts = odd ? r0 + FWG - 1 - tid : r0 + tid;
-    if (ts >= n) continue;
-    Stencil st;
-    stencil_setup<K, W>(st, ts, S, G);
-    uint32_t mask, first;
-    int ec;
-    if constexpr (!W) ec = pairs_count_int<K>(st, S, G, (float)B, (float)ti, &mask, &first);
-    else ec = pairs_count<K, W>(st, S, G, B, two_b2, i_lo, i_hi, &mask, &first);
-    S.fwd[ts] = (uint16_t)ec;
-    S.cnt[ts] = mask;
-    if (FILL_FAST == 3 && ec == 3) S.vrank[ts] = (uint16_t)first;
+  {
+    for (int r0 = 0, odd = 0; r0 < n; r0 += FWG, odd ^= 1) {
+      const int ts = odd ? r0 + FWG - 1 - tid : r0 + tid;
+      if (ufl(ts & ~63) >= n) continue;   // (wave-uniform: the block holds no box)
+      const bool act = ts < n;
+      Stencil st;
+      Span g0, g1;
+      uint32_t mask = 0;
+      int ec = 0;
+      if (act) {
+        stencil_setup<K, W>(st, ts, S, G);
+        if constexpr (!W) ec = pairs_count_int<K>(st, S, G, (float)B, (float)ti, g0, g1, &mask);
+        else ec = pairs_count<K, W>(st, S, G, B, two_b2, i_lo, i_hi, g0, g1, &mask);
+      }
+      const bool top = (ts & 63) == 63;   // the lane that writes the block's end
+      // (lanes past the last box store too: fwd[n] is the end of box n - 1's list unless that
+      // box closes its block; the slots lie within the fwd_blocks(nmax) * 64 begins)
+      if (__ballot(ec != 0) == 0) {   // (no edge in the block, e.g. the last picker's)
+        S.fwd[ts] = 0;
+        if (top) S.bend[ts >> 6] = 0;
+        continue;
+      }
+      // boxes before this one in the block: lanes below (even rounds) or above (odd rounds)
+      const int incl = wave_incl_add32(ec);
+      const int total = __builtin_amdgcn_readlane(incl, 63);
+      uint32_t rb = 0;
+      if ((tid & 63) == 0) rb = (uint32_t)atomicAdd(&H.E, total);
+      const int base = ufl((int)rb);
+      const int off = base + (odd ? total - incl : incl - ec);
+      S.fwd[ts] = (uint16_t)off;
+      if (top) S.bend[ts >> 6] = (uint16_t)(base + total);
+      if (base + total > A.ecap || ec == 0) continue;
+      uint16_t* d = S.dst + off;
+      if (ec <= FILL_FAST) {   // the count kept the targets themselves (ascending)
+        d[0] = (uint16_t)(ec == 2 ? mask >> 16 : mask);
+        if (ec == 2) d[1] = (uint16_t)mask;
+      } else {
+        pairs_fill<K, W>(st, S, G, g0, g1, mask, d, B, two_b2, i_lo, i_hi);
+      }
+      S.flags[ts] = 1;
+    }
+    __syncthreads();
   }
-  __syncthreads();
-  STAMP(3);   // count
+  const int E = ufl(H.E);
+  STAMP(3);   // count + list write (one pass)
   STOP_AFTER(21);
-  
-  // fwd[n] = E is written by the scan; the status is the same in every thread
-  const int E = block_scan_dpp32<FWG>(S.fwd, n, H.redi);
+
+  // the status is the same in every thread
   const int st2 = E == 0 ? RGC_ST_NO_EDGES : (E > A.ecap ? RGC_ST_DEFER : 0);
-  if (tid == 0) {
-    H.E = E;
-    H.status = st2;
-  }
-  STAMP(4);   // scan
+  if (tid == 0) H.status = st2;
+  STAMP(4);   // (the former scan: nothing left but the status)
   STOP_AFTER(22);
   bool cc32 = false;   // the unions ran on u32 parents in cnt
   // QG launches: the workgroup's HBM level-tree slot (claimed here when the edge sources do not
@@ -1523,57 +1575,35 @@ void k_fused(FusedArgs A) {
     }
   }
   if (st2 == 0) {
-    // fill each list (already sorted: position order) and record each edge's source in dst's
-    // unused tail when it has room; then union the edges one thread per edge (lock-free
-    // union-find, balanced across lanes whatever the degrees).  Without room: union per box.
-    const bool src_ok = 2 * E <= A.ecap || (QG && esrc_g != nullptr);
+    // the lists are written (each sorted: position order).  The edges are united one thread
+    // per edge (lock-free union-find on u32 parents in cnt, balanced across lanes whatever the
+    // degrees), which needs each edge's source: written here from the finished lists, in dst's
+    // unused tail when it has room (2 E <= ecap) or in the QG slot in HBM.  With neither: union
+    // per box on the u16 parents.
+    const bool src_hbm = QG && esrc_g != nullptr;
+    const bool src_ok = 2 * E <= A.ecap || src_hbm;
     uint16_t* esrc = S.dst + E;
     // (QG: esrc_g in HBM when dst's tail is short; separate loops keep esrc's LDS accesses
     // ds_* instructions instead of flat ones)
-    const bool src_hbm = QG && esrc_g != nullptr;
-    auto fill_walk = [&](int i, int base, int cnt) {
-      Stencil st;
-      stencil_setup<K, W>(st, i, S, G);
-      pairs_fill<K, W>(st, S, G, S.cnt[i], S.dst + base, cnt, B, two_b2, i_lo, i_hi);
-    };
-    // with room for esrc the unions run after the fill on u32 parents in cnt (each box's
-    // count word is dead once its own thread has read it): identity parents written here
-    for (int r0 = 0, odd = 0; r0 < n; r0 += FWG, odd ^= 1) {   // same order as the count
-      const int ts = odd ? r0 + FWG - 1 - tid : r0 + tid;
-      if (ts >= n) continue;
-      const int i = ts;
-      const int base = S.fwd[i], cnt = (int)S.fwd[i + 1] - base;
-      if (cnt > 0) {
-        uint16_t* d = S.dst + base;
-        if (cnt <= 2) {   // the count kept the targets themselves (ascending)
-          const uint32_t cw0 = S.cnt[ts];
-          d[0] = (uint16_t)(cnt == 2 ? cw0 >> 16 : cw0);
-          if (cnt == 2) d[1] = (uint16_t)cw0;
-        } else if (FILL_FAST == 3 && cnt == 3) {
-          const uint32_t cw0 = S.cnt[ts];
-          d[0] = S.vrank[ts];
-          S.vrank[ts] = 0;   // (CC-size slot: zero for P3)
-          d[1] = (uint16_t)(cw0 >> 16);
-          d[2] = (uint16_t)cw0;
-        } else {
-          fill_walk(i, base, cnt);
-        }
-        S.flags[i] = 1;
+    {
+      for (int i = tid; i < n; i += FWG) {
+        const int base = S.eb(i), cnt = S.ee(i) - base;
         if (src_hbm) {
           for (int e = 0; e < cnt; ++e) esrc_g[base + e] = (uint16_t)i;
         } else if (src_ok) {
           for (int e = 0; e < cnt; ++e) esrc[base + e] = (uint16_t)i;
         } else {
+          const uint16_t* d = S.dst + base;
           for (int e = 0; e < cnt; ++e) {
             S.flags[d[e]] = 1;
             uf_union_lds(S.parent, (uint32_t)i, (uint32_t)d[e]);
           }
         }
+        if (src_ok) S.cnt[i] = (uint32_t)i;
       }
-      if (src_ok) S.cnt[ts] = (uint32_t)ts;
+      __syncthreads();
     }
-    __syncthreads();
-    STAMP(5);   // fill
+    STAMP(5);   // edge sources (or per-box unions) and identity parents
     STOP_AFTER(23);
     if (src_hbm) {
       // sources from HBM (L2) in batches of 8 loads in flight per thread, then the unions
@@ -1612,7 +1642,7 @@ void k_fused(FusedArgs A) {
       if (eb + E <= A.ecap_out) {
         for (int i = tid; i < n; i += FWG) {
           const double2 a = ld_xy<W>(S, i);
-          for (int e = S.fwd[i]; e < (int)S.fwd[i + 1]; ++e) {
+          for (int e = S.eb(i), e1 = S.ee(i); e < e1; ++e) {
             const int h = S.dst[e];
             const double2 b = ld_xy<W>(S, h);
             A.eu[eb + e] = b0 + S.citems[i];
@@ -1636,7 +1666,7 @@ void k_fused(FusedArgs A) {
   STAMP(6);   // union (one thread per edge)
   for (int i = tid; i < n; i += FWG) {
     if (!S.flags[i]) continue;
-    const int e0 = S.fwd[i], e1 = S.fwd[i + 1];
+    const int e0 = S.eb(i), e1 = S.ee(i);
     S.split[i] = (uint16_t)lb16(S.dst, e0, e1, next_picker_end<K>(c.pp, i));   // every node
     const uint32_t r = cc32 ? uf_find32(S.cnt, i) : uf_find_lds(S.parent, i);
     p16_st(S.parent + i, r);
@@ -1680,7 +1710,7 @@ void k_fused(FusedArgs A) {
     // largest CC; ties -> the component whose first edge comes first in the enumeration
     uint64_t best = ~0ULL;
     for (int i = tid; i < n; i += FWG) {
-      const int e0 = S.fwd[i], e1 = S.fwd[i + 1];
+      const int e0 = S.eb(i), e1 = S.ee(i);
       if (e0 == e1) continue;
       const uint32_t r = S.parent[i];
       if (cc_size(r) != cc_max) continue;
@@ -1786,7 +1816,7 @@ void k_fused(FusedArgs A) {
     c.ccur = &H.ccur;
     for (int r = tid; r < n0; r += FWG) {
       uint32_t cntr = 0;
-      if (S.fwd[r] < S.fwd[r + 1] && (!get_cc || S.parent[r] == (uint32_t)target)) {
+      if (S.eb(r) < S.ee(r) && (!get_cc || S.parent[r] == (uint32_t)target)) {
         int mem[K];
         mem[0] = r;
         c.count = 0;

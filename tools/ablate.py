@@ -20,8 +20,11 @@ cfg_name = sys.argv[1] if len(sys.argv) > 1 else "C2"
 n_mg = int(sys.argv[2]) if len(sys.argv) > 2 else 10000
 rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 7
 # (C2_frac: C2 with 3-decimal coordinates, bench.py's by_config entry of that name)
-cfg = synth.SynthConfig(**synth.CONFIGS[cfg_name.replace("_frac", "")], seed=0,
-                        frac=cfg_name.endswith("_frac"))
+# (C2_small: C2's density with a third of the particles, ~300 boxes per micrograph: the size
+# classes where LDS admits eight workgroups per CU and the host picks the 256-thread instance)
+small = dict(n_true=100, width=2400, height=2400) if cfg_name.endswith("_small") else {}
+cfg = synth.SynthConfig(**{**synth.CONFIGS[cfg_name.replace("_frac", "").replace("_small", "")],
+                           **small}, seed=0, frac=cfg_name.endswith("_frac"))
 batch = Batch.pack(cfg.k, cfg.box, synth.batch(cfg, n_mg))
 libs = sorted(glob.glob(os.path.join(ROOT, "abl/*.so"))) + [_lib.LIB_PATH]
 if len(sys.argv) > 4:   # one library only (per-phase PMC passes: tools/gpu_pmc_ablate.sh)
@@ -67,5 +70,6 @@ prev = 0.0
 print(f"{cfg_name} {n_mg} micrographs: device ms (median of {rounds}, interleaved)")
 for p in libs:
     t = float(np.median(times[p]))
-    print(f"  {os.path.basename(p):28s} {t:8.3f} ms   (+{t - prev:7.3f})")
+    print(f"  {os.path.basename(p):28s} {t:8.3f} ms   (+{t - prev:7.3f})"
+          f"   rounds {min(times[p]):.3f} .. {max(times[p]):.3f}")
     prev = t

@@ -15,6 +15,13 @@ counting sort, the half-column stencil and the boustrophedon thread-to-box order
 `synth` micrographs (seed 0) and prints wave iterations per micrograph.  Plain numpy, no GPU.
 
   python tools/p2_trip_model.py [--config C2] [--threads 512] [--micrographs 40] [--frac]
+
+--degrees reports what the list write that follows the count in the same pass works on: the
+forward degree (edges to higher pickers, brute force over the micrograph) of the box each lane
+holds.  A wave-round is one wave in one round, i.e. one aligned block of 64 sorted positions:
+  boxes > 2 edges      boxes whose targets the count cannot keep packed (they walk their mask)
+  wave-rounds, slow    wave-rounds that hold a box, and those that hold a box with > 2 edges
+  write trips          sum over wave-rounds of the largest forward degree (write-loop trips)
 """
 import argparse
 import os
@@ -82,6 +89,50 @@ def wave_iterations(ln, threads):
     return out
 
 
+def forward_degrees(mg, B, order):
+    """Forward degree (JI > 0.3 partners in higher pickers, reference arithmetic) of the box at
+    every sorted position; `order` as returned by box_ranges."""
+    xs = np.concatenate([t[0] for t in mg]).astype(np.float64)
+    ys = np.concatenate([t[1] for t in mg]).astype(np.float64)
+    pk = np.concatenate([np.full(len(t[0]), p) for p, t in enumerate(mg)])
+    xo = np.maximum((np.minimum(xs[:, None], xs[None, :]) + B) - np.maximum(xs[:, None], xs[None, :]), 0.0)
+    yo = np.maximum((np.minimum(ys[:, None], ys[None, :]) + B) - np.maximum(ys[:, None], ys[None, :]), 0.0)
+    inter = xo * yo
+    with np.errstate(invalid="ignore"):
+        edge = (inter / (2 * B * B - inter) > 0.3) & (pk[:, None] < pk[None, :])
+    return edge.sum(axis=1)[order]
+
+
+def degree_report(deg, threads):
+    """One micrograph's {boxes, edges, slow_boxes, wave_rounds, slow_wave_rounds, write_trips}
+    from the forward degrees in sorted-position order (see the module docstring)."""
+    n = len(deg)
+    out = dict(boxes=n, edges=int(deg.sum()), slow_boxes=int((deg > 2).sum()), wave_rounds=0,
+               slow_wave_rounds=0, write_trips=0)
+    tid = np.arange(threads)
+    for rnd, r0 in enumerate(range(0, n, threads)):
+        ts = r0 + threads - 1 - tid if rnd & 1 else r0 + tid
+        act = (ts < n).reshape(threads // 64, 64)
+        dw = np.zeros(threads, np.int64)
+        dw[ts < n] = deg[ts[ts < n]]
+        dw = dw.reshape(threads // 64, 64)                         # [wave, lane]
+        out["wave_rounds"] += int(act.any(axis=1).sum())
+        out["slow_wave_rounds"] += int((dw > 2).any(axis=1).sum())
+        out["write_trips"] += int(dw.max(axis=1).sum())
+    return out
+
+
+def degree_model(config, threads, n_mg, frac=False):
+    """degree_report averaged over n_mg synth micrographs (seed 0)."""
+    cfg = synth.SynthConfig(**synth.CONFIGS[config], seed=0, frac=frac)
+    tot = {}
+    for mg in synth.batch(cfg, n_mg):
+        order = box_ranges(mg, float(cfg.box))[2]
+        for k, v in degree_report(forward_degrees(mg, float(cfg.box), order), threads).items():
+            tot[k] = tot.get(k, 0) + v
+    return {k: v / n_mg for k, v in tot.items()}
+
+
 def model(config, threads, n_mg, frac=False):
     cfg = synth.SynthConfig(**synth.CONFIGS[config], seed=0, frac=frac)
     tot = np.zeros(4, np.int64)
@@ -97,9 +148,23 @@ if __name__ == "__main__":
     ap.add_argument("--threads", type=int, default=0, help="workgroup size (multiple of 64)")
     ap.add_argument("--micrographs", type=int, default=0)
     ap.add_argument("--frac", action="store_true", help="3-decimal coordinates (C2_frac)")
+    ap.add_argument("--degrees", action="store_true",
+                    help="forward degrees per wave-round (the one-pass list write)")
     a = ap.parse_args()
     threads = a.threads or DEFAULT_THREADS[a.config]
     n_mg = a.micrographs or (40 if a.config == "C2" else 20)
+    if a.degrees:
+        d = degree_model(a.config, threads, n_mg, a.frac)
+        print(f"{a.config}{'_frac' if a.frac else ''}: {n_mg} micrographs, {threads} threads, "
+              f"per micrograph")
+        print(f"  boxes / forward edges        {d['boxes']:8.1f} / {d['edges']:.1f}")
+        print(f"  boxes with > 2 edges         {d['slow_boxes']:8.1f}  "
+              f"({100 * d['slow_boxes'] / d['boxes']:.1f} %)")
+        print(f"  wave-rounds holding a box    {d['wave_rounds']:8.1f}")
+        print(f"  ... one with > 2 edges       {d['slow_wave_rounds']:8.1f}  "
+              f"({100 * d['slow_wave_rounds'] / d['wave_rounds']:.0f} %)")
+        print(f"  write-loop trips             {d['write_trips']:8.1f}")
+        sys.exit(0)
     rg, pg, fl, pf = model(a.config, threads, n_mg, a.frac)
     print(f"{a.config}{'_frac' if a.frac else ''}: {n_mg} micrographs, {threads} threads, "
           f"count-loop wave iterations per micrograph")

@@ -40,7 +40,10 @@ st = raw[:, :13]
 nch, ncl = raw[:, 14], raw[:, 15]
 print(f"BFS root chunks per micrograph: mean {nch.mean():.2f} p50 {np.median(nch):.0f} "
       f"max {nch.max()} (0 = per-root DFS fallback: {(nch == 0).sum()}); cliques mean {ncl.mean():.0f}")
-names = ["P0 load+bbox", "P1 grid+sort", "P2a count", "P2b fwd scan", "P2c fill",
+# (the 13 stamp indices are fixed, so stamp files of older libraries still line up: since P2
+# runs in one pass, stamp 4 closes an empty phase (it was the fwd scan) and stamp 5 the loop
+# that writes the edge sources behind the targets (it was the fill))
+names = ["P0 load+bbox", "P1 grid+sort", "P2a count+write", "P2b (empty)", "P2c sources",
          "P3a union", "P3b CC stats", "P4a DFS+queue", "P4b scan+reserve", "P5 rank",
          "P6a score staging", "P6b epilogue"]
 valid = (st != 0).all(axis=1)

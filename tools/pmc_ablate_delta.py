@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Per-phase marginal PMC counts from a tools/gpu_pmc_ablate.sh log (stopN builds + product).
 
+P2's sub-phases: stop21 = after the one pass (count + list write), stop22 = after the status
+that follows it (nothing to measure since the scan is gone: the build is kept so that the
+rows of older logs line up), stop23 = after the loop that writes the edge sources (or unites per
+box where they have no room), stop2 = after the edge-parallel union.
+
   python tools/pmc_ablate_delta.py LOG
 """
 import sys
