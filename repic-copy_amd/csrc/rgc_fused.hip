@@ -59,6 +59,26 @@ constexpr int MAXW = 16;            // reduction slots: up to 1024-thread workgr
 // 1024: C3's ~4.1k boxes all stay in registers, VGPRs to spare at 4 waves per SIMD; boxes past
 // RB * NT are re-read from HBM in each of P0's and P1's passes)
 constexpr int fused_rb(int nt) { return nt <= 256 ? 4 : nt >= 1024 ? 5 : 2; }
+// Phases whose per-box / per-edge / per-vertex loops keep two items of a thread in flight
+// (in_flight).  None in the product: every phase runs its staged body one item at a time,
+// which is where the measured gain is; each pair form on top of it was inside the spread or
+// slower (profiles/r11f).  RGC_TWO_MASK selects phases for timing
+// experiments (`make xp X=M4 XDEF=-DRGC_TWO_MASK=4u`, tools/ablate.py), within what the
+// instance's registers allow without crossing an occupancy step.
+enum : unsigned { TWO_P1 = 1, TWO_P2C = 2, TWO_P3A = 4, TWO_P3B = 8, TWO_P5 = 16, TWO_P6A = 32 };
+#ifndef RGC_TWO_MASK
+#define RGC_TWO_MASK 0u
+#endif
+constexpr unsigned fused_two(int k, bool wide, int nt) {
+  unsigned m = RGC_TWO_MASK;
+  // P1 holds all RB register boxes of a thread at once: with 4 or 5 of them the 256-thread
+  // instances spill and the 1024-thread ones lose a wave per SIMD
+  if (fused_rb(nt) != 2) m &= ~TWO_P1;
+  // K >= 4: P5's two-vertex rank loop takes K = 5 / 768 threads and K = 4 / 1024 from 72 to 73
+  // VGPRs, one allocation granule up
+  if (k >= 4) m &= ~TWO_P5;
+  return m;
+}
 
 struct FusedHdr {
   // reduction scratch: the single-value reductions alias the 4-way one (every reduction
@@ -250,16 +270,32 @@ __device__ __forceinline__ uint32_t uf_find32(uint32_t* parent, uint32_t x) {
     x = gp;
   }
 }
-__device__ __forceinline__ void uf_union32(uint32_t* parent, uint32_t a, uint32_t b) {
+// the find of x given p, a value loaded from parent[x] earlier (a stale p is still an ancestor
+// of x, or x itself if x was a root then: the race every find here has with a concurrent link)
+__device__ __forceinline__ uint32_t uf_find32p(uint32_t* parent, uint32_t x, uint32_t p) {
+  if (p == x) return x;
+  const uint32_t gp = lds_ld(parent + p);
+  if (gp != p) lds_st(parent + x, gp);
+  return uf_find32(parent, gp);
+}
+// union of a and b given pa, pb loaded from parent[a], parent[b]: the caller issues those loads
+// (of both endpoints, and of every edge it has in flight) together
+__device__ __forceinline__ void uf_union32p(uint32_t* parent, uint32_t a, uint32_t pa,
+                                            uint32_t b, uint32_t pb) {
+  a = uf_find32p(parent, a, pa);
+  b = uf_find32p(parent, b, pb);
   for (;;) {
-    a = uf_find32(parent, a);
-    b = uf_find32(parent, b);
     if (a == b) return;
     if (a < b) { const uint32_t t = a; a = b; b = t; }
     const uint32_t old = atomicMin(parent + a, b);
     if (old == a) return;
-    a = old;
+    a = uf_find32(parent, old);
+    b = uf_find32(parent, b);
   }
+}
+__device__ __forceinline__ void uf_union32(uint32_t* parent, uint32_t a, uint32_t b) {
+  const uint32_t pa = lds_ld(parent + a), pb = lds_ld(parent + b);
+  uf_union32p(parent, a, pa, b, pb);
 }
 
 template <int K>
@@ -302,6 +338,70 @@ __device__ __forceinline__ int lb16(const uint16_t* a, int lo, int hi, int v) {
     if ((int)a[mid] < v) lo = mid + 1; else hi = mid;
   }
   return lo;
+}
+
+// ---- several items of one thread in flight.  A per-item loop `for (i = tid; i < n; i += S)`
+// runs each item as its own chain of dependent LDS round trips, and the compiler cannot move
+// item 2's loads above item 1's stores and atomics (same address space).  The loops below are
+// written as a body over N items (i = first + j * S, j < N), each stage an `each` call over
+// all N before the next stage starts, so the N loads of a stage are issued before the first
+// wait.  in_flight runs the body with N = NI for the thread's first NI items and with N = 1 for
+// any further ones (NI = 1: the plain loop).  A wave whose lanes all hold NI items (every wave
+// of the second round but the last) runs the body without the per-item tests: their exec
+// regions would each wait for everything in flight before them.
+template <int N, int S, bool ALL>
+struct Items {
+  static constexpr int n = N;
+  // fn(j, i) for each of the N items that exists
+  template <class F>
+  __device__ __forceinline__ void each(int first, int end, F&& fn) const {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const int i = first + j * S;
+      if (ALL || i < end) fn(j, i);
+    }
+  }
+};
+// (first = the lane's index in its wave + a wave-uniform multiple of 64)
+template <int N, int S>
+__device__ __forceinline__ bool wave_holds_all(int first, int n) {
+#ifdef RGC_NO_ALL   // (timing experiments: the pair forms without the full-wave path)
+  return false;
+#endif
+  return __builtin_amdgcn_readfirstlane(first & ~63) + 63 + (N - 1) * S < n;
+}
+template <int NI, int S, class Body>
+__device__ __forceinline__ void in_flight(int first, int n, Body&& body) {
+  if constexpr (NI > 1) {
+    if (wave_holds_all<NI, S>(first, n)) body(Items<NI, S, true>{}, first);
+    else body(Items<NI, S, false>{}, first);
+  }
+  for (int i = first + (NI > 1 ? NI * S : 0); i < n; i += S) body(Items<1, S, false>{}, i);
+}
+
+// lb16 for N searches at once: every step loads all N probes before the first compare (a
+// finished or empty search, lo >= hi, probes a[0] and keeps its bounds)
+template <int N>
+__device__ __forceinline__ void lb16n(const uint16_t* a, int (&lo)[N], int (&hi)[N],
+                                      const int (&v)[N]) {
+  for (;;) {
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < N; ++j) any |= lo[j] < hi[j];
+    if (!any) return;
+    int mid[N], x[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      mid[j] = (lo[j] + hi[j]) >> 1;
+      x[j] = a[lo[j] < hi[j] ? mid[j] : 0];
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const bool act = lo[j] < hi[j], up = x[j] < v[j];
+      lo[j] = act && up ? mid[j] + 1 : lo[j];
+      hi[j] = act && !up ? mid[j] : hi[j];
+    }
+  }
 }
 
 __device__ __forceinline__ bool contains16(const uint16_t* a, int lo, int hi, int v) {
@@ -1315,6 +1415,29 @@ void k_fused(FusedArgs A) {
     }
     for (int i = tid + RB * FWG; i < n; i += FWG) fn(i, ax[b0 + i], ay[b0 + i]);
   };
+  // the staged form (in_flight): body(Items<N, ..>, first, xy) with xy(j, i) the coordinates of
+  // item j; the RB register boxes of a thread run as one body when TWO
+  constexpr unsigned TWOM = fused_two(K, W, NT);
+  constexpr bool TWO = (TWOM & TWO_P1) != 0;
+  // items in flight of each phase's loops over positions, edges or vertices
+  constexpr int NF_P2C = TWOM & TWO_P2C ? 2 : 1, NF_P3A = TWOM & TWO_P3A ? 2 : 1,
+                NF_P3B = TWOM & TWO_P3B ? 2 : 1, NF_P5 = TWOM & TWO_P5 ? 2 : 1,
+                NF_P6A = TWOM & TWO_P6A ? 2 : 1;
+  auto each_box_staged = [&](auto&& body) {
+    if constexpr (TWO) {
+      auto xy = [&](int j, int) { return make_double2(rx[j], ry[j]); };
+      if (wave_holds_all<RB, FWG>(tid, n)) body(Items<RB, FWG, true>{}, tid, xy);
+      else body(Items<RB, FWG, false>{}, tid, xy);
+    } else {
+#pragma unroll
+      for (int j = 0; j < RB; ++j)
+        body(Items<1, FWG, false>{}, tid + j * FWG,
+             [&](int, int) { return make_double2(rx[j], ry[j]); });
+    }
+    for (int i = tid + RB * FWG; i < n; i += FWG)
+      body(Items<1, FWG, false>{}, i,
+           [&](int, int ii) { return make_double2(ax[b0 + ii], ay[b0 + ii]); });
+  };
   // bounding box on floats for the f32 layout (exact there; a micrograph with inexact
   // coordinates is deferred to the f64 layout, where it is computed in f64)
   using BT = typename std::conditional<W, double, float>::type;
@@ -1451,24 +1574,47 @@ void k_fused(FusedArgs A) {
   block_scan_dpp32<FWG>(S.cstart, nk + 2, H.redi);
   // arrival order into fwd (free until P2), made deterministic by the placement pass
   uint16_t* arrival = S.fwd;
-  each_box([&](int i, double, double) {
-    const int q = S.pos[i];
-    const int sh = 16 * (q & 1);
-    const int t = (atomicAdd(&cw[q >> 1], 1u << sh) >> sh) & 0xFFFF;
-    arrival[t] = (uint16_t)i;
+  each_box_staged([&](auto it, int first, auto&&) {
+    constexpr int N = decltype(it)::n;
+    int q[N];
+    uint32_t t[N];
+    it.each(first, n, [&](int j, int i) { q[j] = S.pos[i]; });
+    it.each(first, n, [&](int j, int) {
+      t[j] = atomicAdd(&cw[q[j] >> 1], 1u << (16 * (q[j] & 1)));
+    });
+    it.each(first, n, [&](int j, int i) {
+      arrival[(t[j] >> (16 * (q[j] & 1))) & 0xFFFF] = (uint16_t)i;
+    });
   });
   __syncthreads();
-  // placement: by local index inside each bucket (buckets hold a few boxes)
-  each_box([&](int i, double xv, double yv) {
-    const int q = S.pos[i];
-    const int lo = S.cstart[q - 1], hi = S.cstart[q];
-    int t = lo;
+  // placement: by local index inside each bucket (buckets hold a few boxes; the items' buckets
+  // are walked in one loop over the longest, a shorter one re-reading its first entry)
+  each_box_staged([&](auto it, int first, auto&& xy) {
+    constexpr int N = decltype(it)::n;
+    int q[N], lo[N] = {}, len[N] = {}, t[N];
+    it.each(first, n, [&](int j, int i) { q[j] = S.pos[i]; });
+    it.each(first, n, [&](int j, int) {
+      lo[j] = S.cstart[q[j] - 1];
+      len[j] = (int)S.cstart[q[j]] - lo[j];
+    });
+    int ml = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) { ml = max(ml, len[j]); t[j] = lo[j]; }
 #pragma nounroll
-    for (int u = lo; u < hi; ++u) t += (int)arrival[u] < i ? 1 : 0;
-    S.scell[t] = (uint16_t)(q - 1);
-    S.citems[t] = (uint16_t)i;
-    S.pos[i] = (uint16_t)t;
-    st_xy<W>(S, t, xv, yv);
+    for (int u = 0; u < ml; ++u) {
+      int a[N];
+#pragma unroll
+      for (int j = 0; j < N; ++j) a[j] = arrival[lo[j] + (u < len[j] ? u : 0)];
+#pragma unroll
+      for (int j = 0; j < N; ++j) t[j] += (u < len[j] && a[j] < first + j * FWG) ? 1 : 0;
+    }
+    it.each(first, n, [&](int j, int i) {
+      const double2 v = xy(j, i);
+      S.scell[t[j]] = (uint16_t)(q[j] - 1);
+      S.citems[t[j]] = (uint16_t)i;
+      S.pos[i] = (uint16_t)t[j];
+      st_xy<W>(S, t[j], v.x, v.y);
+    });
   });
   __syncthreads();
   // picker bounds in position space: grid p occupies [pp[p], pp[p+1]); non-finite boxes follow
@@ -1586,21 +1732,28 @@ void k_fused(FusedArgs A) {
     // (QG: esrc_g in HBM when dst's tail is short; separate loops keep esrc's LDS accesses
     // ds_* instructions instead of flat ones)
     {
-      for (int i = tid; i < n; i += FWG) {
-        const int base = S.eb(i), cnt = S.ee(i) - base;
-        if (src_hbm) {
-          for (int e = 0; e < cnt; ++e) esrc_g[base + e] = (uint16_t)i;
-        } else if (src_ok) {
-          for (int e = 0; e < cnt; ++e) esrc[base + e] = (uint16_t)i;
-        } else {
-          const uint16_t* d = S.dst + base;
-          for (int e = 0; e < cnt; ++e) {
-            S.flags[d[e]] = 1;
-            uf_union_lds(S.parent, (uint32_t)i, (uint32_t)d[e]);
+      in_flight<NF_P2C, FWG>(tid, n, [&](auto it, int first) {
+        constexpr int N = decltype(it)::n;
+        int base[N], cnt[N];
+        it.each(first, n, [&](int j, int i) {
+          base[j] = S.eb(i);
+          cnt[j] = S.ee(i) - base[j];
+        });
+        it.each(first, n, [&](int j, int i) {
+          if (src_hbm) {
+            for (int e = 0; e < cnt[j]; ++e) esrc_g[base[j] + e] = (uint16_t)i;
+          } else if (src_ok) {
+            for (int e = 0; e < cnt[j]; ++e) esrc[base[j] + e] = (uint16_t)i;
+          } else {
+            const uint16_t* d = S.dst + base[j];
+            for (int e = 0; e < cnt[j]; ++e) {
+              S.flags[d[e]] = 1;
+              uf_union_lds(S.parent, (uint32_t)i, (uint32_t)d[e]);
+            }
           }
-        }
-        if (src_ok) S.cnt[i] = (uint32_t)i;
-      }
+          if (src_ok) S.cnt[i] = (uint32_t)i;
+        });
+      });
       __syncthreads();
     }
     STAMP(5);   // edge sources (or per-box unions) and identity parents
@@ -1626,11 +1779,19 @@ void k_fused(FusedArgs A) {
       }
       __syncthreads();
     } else if (src_ok) {
-      for (int e = tid; e < E; e += FWG) {
-        const uint32_t h = S.dst[e];
-        S.flags[h] = 1;
-        uf_union32(S.cnt, esrc[e], h);
-      }
+      in_flight<NF_P3A, FWG>(tid, E, [&](auto it, int first) {
+        constexpr int N = decltype(it)::n;
+        uint32_t a[N], h[N], pa[N], ph[N];
+        it.each(first, E, [&](int j, int e) { a[j] = esrc[e]; h[j] = S.dst[e]; });
+        it.each(first, E, [&](int j, int) {
+          pa[j] = lds_ld(S.cnt + a[j]);
+          ph[j] = lds_ld(S.cnt + h[j]);
+        });
+        it.each(first, E, [&](int j, int) {
+          S.flags[h[j]] = 1;
+          uf_union32p(S.cnt, a[j], pa[j], h[j], ph[j]);
+        });
+      });
       __syncthreads();
     }
     cc32 = src_ok;
@@ -1664,14 +1825,28 @@ void k_fused(FusedArgs A) {
   
   // ---- P3: connected components: the unions ran in the P2 fill; compress, count sizes
   STAMP(6);   // union (one thread per edge)
-  for (int i = tid; i < n; i += FWG) {
-    if (!S.flags[i]) continue;
-    const int e0 = S.eb(i), e1 = S.ee(i);
-    S.split[i] = (uint16_t)lb16(S.dst, e0, e1, next_picker_end<K>(c.pp, i));   // every node
-    const uint32_t r = cc32 ? uf_find32(S.cnt, i) : uf_find_lds(S.parent, i);
-    p16_st(S.parent + i, r);
-    atomicAdd(&ccsz[r >> 1], 1u << (16 * (r & 1)));
-  }
+  in_flight<NF_P3B, FWG>(tid, n, [&](auto it, int first) {
+    constexpr int N = decltype(it)::n;
+    int f[N] = {}, lo[N] = {}, hi[N] = {}, v[N] = {};
+    uint32_t p[N];
+    it.each(first, n, [&](int j, int i) {
+      f[j] = S.flags[i];
+      lo[j] = S.eb(i);
+      hi[j] = S.ee(i);
+      if (cc32) p[j] = lds_ld(S.cnt + i);
+      v[j] = next_picker_end<K>(c.pp, i);
+    });
+#pragma unroll
+    for (int j = 0; j < N; ++j) hi[j] = f[j] ? hi[j] : lo[j];
+    lb16n<N>(S.dst, lo, hi, v);
+    it.each(first, n, [&](int j, int i) {
+      if (!f[j]) return;
+      S.split[i] = (uint16_t)lo[j];   // every node
+      const uint32_t r = cc32 ? uf_find32p(S.cnt, i, p[j]) : uf_find_lds(S.parent, i);
+      p16_st(S.parent + i, r);
+      atomicAdd(&ccsz[r >> 1], 1u << (16 * (r & 1)));
+    });
+  });
   __syncthreads();
   auto cc_size = [&](uint32_t r) { return (int)((ccsz[r >> 1] >> (16 * (r & 1))) & 0xFFFF); };
   int nodes, cc_max;
@@ -1681,12 +1856,21 @@ void k_fused(FusedArgs A) {
     // nodes << 16 | roots (both <= n < 2^16) in one 32-bit sum
     int nr = 0;
     int mx = 0;
-    for (int i = tid; i < n; i += FWG) {
-      if (S.flags[i]) {
+    in_flight<NF_P3B, FWG>(tid, n, [&](auto it, int first) {
+      constexpr int N = decltype(it)::n;
+      int f[N], p[N];
+      uint32_t sz[N];
+      it.each(first, n, [&](int j, int i) {
+        f[j] = S.flags[i];
+        p[j] = S.parent[i];
+        sz[j] = ccsz[i >> 1];
+      });
+      it.each(first, n, [&](int j, int i) {
+        if (!f[j]) return;
         nr += 1 << 16;
-        if (S.parent[i] == (uint32_t)i) { nr += 1; mx = max(mx, cc_size(i)); }
-      }
-    }
+        if (p[j] == i) { nr += 1; mx = max(mx, (int)((sz[j] >> (16 * (i & 1))) & 0xFFFF)); }
+      });
+    });
     nr = wave_incl_add32(nr);
     mx = wave_incl_max32(mx);
     if ((tid & 63) == 63) { H.redi[tid >> 6] = nr; reinterpret_cast<int*>(H.redu)[tid >> 6] = mx; }
@@ -1880,37 +2064,73 @@ void k_fused(FusedArgs A) {
     auto xbucket = [&](CT xv) { return (int)fmin((xv - minx) * xbs, nlast); };
     for (int q = tid; q <= (n + 1) / 2; q += FWG) bw[q] = 0;
     __syncthreads();
-    for (int t = tid; t < n; t += FWG) {
-      if (S.flags[t] != 3) continue;
-      const int q = xbucket(ld(t).x);
-      const int sh = 16 * (q & 1);
-      S.vrank[t] = (uint16_t)((atomicAdd(&bw[q >> 1], 1u << sh) >> sh) & 0xFFFFu);
-    }
+    in_flight<NF_P5, FWG>(tid, n, [&](auto it, int first) {
+      constexpr int N = decltype(it)::n;
+      int f[N], q[N];
+      uint32_t r[N];
+      CT x[N];
+      it.each(first, n, [&](int j, int t) { f[j] = S.flags[t]; x[j] = ld(t).x; });
+      it.each(first, n, [&](int j, int) {
+        if (f[j] != 3) return;
+        q[j] = xbucket(x[j]);
+        r[j] = atomicAdd(&bw[q[j] >> 1], 1u << (16 * (q[j] & 1)));
+      });
+      it.each(first, n, [&](int j, int t) {
+        if (f[j] == 3) S.vrank[t] = (uint16_t)((r[j] >> (16 * (q[j] & 1))) & 0xFFFFu);
+      });
+    });
     __syncthreads();
     const int V = block_scan_dpp32<FWG>(bcnt, n, H.redi);
     if (tid == 0) { H.V = (int)V; bcnt[n] = (uint16_t)V; }
-    for (int t = tid; t < n; t += FWG) {
-      if (S.flags[t] != 3) continue;
-      blist[bcnt[xbucket(ld(t).x)] + S.vrank[t]] = (uint16_t)t;
-    }
+    in_flight<NF_P5, FWG>(tid, n, [&](auto it, int first) {
+      constexpr int N = decltype(it)::n;
+      int f[N], vr[N], bb[N];
+      CT x[N];
+      it.each(first, n, [&](int j, int t) {
+        f[j] = S.flags[t];
+        x[j] = ld(t).x;
+        vr[j] = S.vrank[t];
+      });
+      it.each(first, n, [&](int j, int) { if (f[j] == 3) bb[j] = bcnt[xbucket(x[j])]; });
+      it.each(first, n, [&](int j, int t) {
+        if (f[j] == 3) blist[bb[j] + vr[j]] = (uint16_t)t;
+      });
+    });
     __syncthreads();
     // ranks over the dense bucket-ordered vertex list (every lane holds a vertex; the
-    // position loop above skips the non-vertices)
-    for (int u0 = tid; u0 < V; u0 += FWG) {
-      const int t = blist[u0];
-      const int vi = S.citems[t];
-      const CT2 v = ld(t);
-      const int b = xbucket(v.x);
-      const int lo = bcnt[b], hi = bcnt[b + 1];
-      uint32_t rk = lo;
-      for (int u = lo; u < hi; ++u) {
-        const int tu = blist[u];
-        const CT2 w = ld(tu);
-        const int ui = S.citems[tu];
-        rk += (w.x < v.x) || (w.x == v.x && (w.y < v.y || (w.y == v.y && ui < vi)));
+    // position loop above skips the non-vertices).  The items' buckets are walked in one loop
+    // over the longest, a shorter one re-reading its first entry.
+    in_flight<NF_P5, FWG>(tid, V, [&](auto it, int first) {
+      constexpr int N = decltype(it)::n;
+      int t[N] = {}, vi[N] = {}, lo[N] = {}, len[N] = {};
+      CT2 v[N] = {};
+      uint32_t rk[N];
+      it.each(first, V, [&](int j, int u0) { t[j] = blist[u0]; });
+      it.each(first, V, [&](int j, int) { vi[j] = S.citems[t[j]]; v[j] = ld(t[j]); });
+      it.each(first, V, [&](int j, int) {
+        const int b = xbucket(v[j].x);
+        lo[j] = bcnt[b];
+        len[j] = (int)bcnt[b + 1] - lo[j];
+      });
+      int ml = 0;
+#pragma unroll
+      for (int j = 0; j < N; ++j) { ml = max(ml, len[j]); rk[j] = lo[j]; }
+#pragma nounroll
+      for (int u = 0; u < ml; ++u) {
+        int tu[N], ui[N];
+        CT2 w[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) tu[j] = blist[lo[j] + (u < len[j] ? u : 0)];
+#pragma unroll
+        for (int j = 0; j < N; ++j) { w[j] = ld(tu[j]); ui[j] = S.citems[tu[j]]; }
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+          rk[j] += u < len[j] && ((w[j].x < v[j].x) ||
+                                  (w[j].x == v[j].x &&
+                                   (w[j].y < v[j].y || (w[j].y == v[j].y && ui[j] < vi[j]))));
       }
-      S.vrank[t] = (uint16_t)rk;
-    }
+      it.each(first, V, [&](int j, int) { S.vrank[t[j]] = (uint16_t)rk[j]; });
+    });
     if (tid == 0) H.base = (int64_t)resv;   // (the reservation's round trip ends here)
     __syncthreads();
     // every thread reads the base; an output overflow skips P6 (the host regrows and re-runs)
@@ -1928,8 +2148,18 @@ void k_fused(FusedArgs A) {
     // scores of the clique vertices into LDS by row rank when they fit in parent..scell
     c.S.vstaged = 8 * H.V <= L.off_citems - L.off_parent;
     if (c.S.vstaged) {
-      for (int t = tid; t < n; t += FWG)
-        if (S.flags[t] == 3) c.S.vscore[S.vrank[t]] = c.score[b0 + S.citems[t]];
+      in_flight<NF_P6A, FWG>(tid, n, [&](auto it, int first) {
+        constexpr int N = decltype(it)::n;
+        int f[N], vr[N], li[N];
+        double sc[N];
+        it.each(first, n, [&](int j, int t) {
+          f[j] = S.flags[t];
+          vr[j] = S.vrank[t];
+          li[j] = S.citems[t];
+        });
+        it.each(first, n, [&](int j, int) { if (f[j] == 3) sc[j] = c.score[b0 + li[j]]; });
+        it.each(first, n, [&](int j, int) { if (f[j] == 3) c.S.vscore[vr[j]] = sc[j]; });
+      });
       __syncthreads();
     }
 
