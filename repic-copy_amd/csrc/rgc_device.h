@@ -259,6 +259,25 @@ __device__ __forceinline__ T block_excl_scan_dpp(T v, T* lds, T* total) {
   return pre + inc - v;
 }
 
+// The same for a 32-bit sum (total < 2^31) on the bound_ctrl DPP scan: one move and one add per
+// step.  ONE barrier, same contract for lds (BS / 64 ints).
+template <int BS>
+__device__ __forceinline__ int block_excl_scan_add32(int v, int* lds, int* total) {
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int inc = wave_incl_add32(v);
+  if (l == 63) lds[w] = inc;
+  __syncthreads();
+  int pre = inc - v, tot = 0;
+#pragma unroll
+  for (int i = 0; i < BS / 64; ++i) {
+    const int x = lds[i];
+    pre += (i < w) ? x : 0;
+    tot += x;
+  }
+  *total = tot;
+  return pre;
+}
+
 // In-place exclusive scan of a[0..n) in LDS (each thread a contiguous chunk), a[n] = total,
 // ending with a barrier: two barriers in all, the caller guaranteeing one before (see above).
 // A = uint16_t (totals < 2^16) or uint32_t.

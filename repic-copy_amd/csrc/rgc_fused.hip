@@ -80,6 +80,15 @@ constexpr unsigned fused_two(int k, bool wide, int nt) {
   return m;
 }
 
+// Barriers taken off the workgroup's chain by moving work in front of one that is there anyway
+// (RGC_BAR_MASK selects them for timing experiments): P5's counter zeroing in front of P4's
+// reservation barrier; P3b's stats summed behind P4's barriers when --get_cc is off.
+enum : unsigned { BAR_P5_ZERO = 1, BAR_P3B_STATS = 2 };
+#ifndef RGC_BAR_MASK
+#define RGC_BAR_MASK 3u
+#endif
+constexpr unsigned fused_bars() { return RGC_BAR_MASK; }
+
 struct FusedHdr {
   // reduction scratch: the single-value reductions alias the 4-way one (every reduction
   // starts behind a barrier)
@@ -770,6 +779,29 @@ __device__ __forceinline__ uint2 we_pack(const int (&mm)[4], int d, int h) {
   t[d] = h;
   return make_uint2((uint32_t)t[0] | ((uint32_t)t[1] << 16), (uint32_t)t[2] | ((uint32_t)t[3] << 16));
 }
+// One-trip form: a level (or the root pass) of at most NT entries runs as one staged body per
+// thread, count to fill in registers around a one-barrier scan: two barriers per level instead
+// of four, no count / mask round trip through LDS.  Levels above NT entries take the general
+// count / scan / fill form; both produce the same entry order, so a micrograph may mix them.
+// Instances: K <= 3 with up to 768 threads.  The others pay for the second form in registers
+// (`make resources`): K = 3 / 1024 and every K = 4 instance drop an
+// occupancy step, K = 5 / 768 (f64 layout) grows its scratch and K = 5 / 768 (f32) drops a step,
+// and so on up to K = 8; they keep the general form alone.
+// RGC_BFS_ONE selects the parts for timing experiments (`make xp X=B0 XDEF=-DRGC_BFS_ONE=0`):
+// 1 the levels, 2 the root pass, 4 every instance.
+#ifndef RGC_BFS_ONE
+#define RGC_BFS_ONE 3
+#endif
+enum : int { ONE_LEVELS = 1, ONE_ROOTS = 2, ONE_EVERY = 4 };
+constexpr bool bfs_one_trip(int k, int nt, int part) {
+  return (RGC_BFS_ONE & part) != 0 && ((RGC_BFS_ONE & ONE_EVERY) != 0 || (k <= 3 && nt <= 768));
+}
+// Per-wave slots of the one-trip scans.  Not redi / redu: P3b's stats reduction reads those
+// up to the first barrier P4 takes, which is the root pass's scan barrier.  Consecutive
+// one-trip scans are separated by the barrier behind the fill (or, on overflow, behind the
+// capacity check), so one set of slots serves every level.
+__device__ __forceinline__ int* bfs_scan_slots(FusedHdr& H) { return reinterpret_cast<int*>(H.red64); }
+
 template <int K, int D, int NT, bool WE = false>
 struct BfsLevel {
   // prefix members of entry e of level D (D members, compile-time indices only)
@@ -819,55 +851,76 @@ struct BfsLevel {
       out.fit = fminf(out.fit, 0.999f);
       return out;
     }
-    uint32_t* MK = reinterpret_cast<uint32_t*>(q + tb);
-    uint32_t* CN = MK + nD;
-    for (int e = tid; e < nD; e += NT) {
-      int mm[K];
-      prefix(q, lvl, (uint32_t)e, mm);
-      const int m = mm[D - 1];
-      const int lo = S.eb(m), hi = seg_end<REWALK>(S, pp, m);
-      uint32_t mask = 0, cnt = 0;
-      // an extension h (picker D) must be adjacent to every earlier member: the graph's edges
-      // are exactly the pairs of different pickers with JI > 0.3, so instead of a binary
-      // search of h in each member's sorted list (three dependent LDS loads each), P2's own
-      // test on the two boxes' coordinates decides it (ep.edge: the same function on the same
-      // LDS values, so the same answer); the members' coordinates stay in registers
-      typename EP::CT mc[K > 2 ? K - 2 : 1];
-#pragma unroll
-      for (int d = 0; d < D - 1; ++d) mc[d] = ep.pt(S, mm[d]);
-      for (int t = lo; t < hi; ++t) {
-        const int h = S.dst[t];
-        const typename EP::CT ch = ep.pt(S, h);
-        bool ok = true;
-#pragma unroll
-        for (int d = 0; d < D - 1; ++d) ok &= ep.edge(mc[d], ch);
-        cnt += ok ? 1u : 0u;
-        mask |= (ok && t - lo < 32) ? (1u << (t - lo)) : 0u;
-      }
-      MK[e] = mask;
-      CN[e] = cnt;
-    }
-    __syncthreads();
-    // (32-bit scan: nD <= 65535 entries of at most n <= 4608 extensions each, < 2^31)
-    const int64_t nN = ufl(block_scan_dpp32<NT>(CN, (int)nD, H.redi));
     constexpr bool last = D + 1 == K;
     const int nb = ufl((lvl[D] + ES * (int)nD + 7) & ~7);   // next level starts here
-    if (K >= 4) {
-      const float f = fminf(bfs_fit(nN, 65535), bfs_fit(nN * (last ? ES + 2 : ES), tb - nb));
-      out.fit = fminf(out.fit, f);
-    }
-    if (nN > 65535 || nN * (last ? ES + 2 : ES) > tb - nb) {
-      out.C = -1;
-      out.fit = fminf(out.fit, 0.999f);
-      return out;
-    }
-    for (int e = tid; e < nD; e += NT) {
-      int mm[K];
-      prefix(q, lvl, (uint32_t)e, mm);
-      const int m = mm[D - 1];
-      const int lo = S.eb(m), hi = seg_end<REWALK>(S, pp, m);
-      const uint32_t mask = MK[e];
-      uint32_t o = CN[e];
+    // the next level's capacity checks, on its size nN (both forms)
+    auto next_fits = [&](int64_t nN) {
+      if (K >= 4) {
+        const float f = fminf(bfs_fit(nN, 65535), bfs_fit(nN * (last ? ES + 2 : ES), tb - nb));
+        out.fit = fminf(out.fit, f);
+      }
+      if (nN > 65535 || nN * (last ? ES + 2 : ES) > tb - nb) {
+        out.C = -1;
+        out.fit = fminf(out.fit, 0.999f);
+        return false;
+      }
+      return true;
+    };
+    // a child of entry e (prefix mm) with last member h at index o of the next level
+    auto put = [&](uint32_t e, const int (&mm)[K], int h, uint32_t o, int64_t nN) {
+      if constexpr (WE) {
+        int m4[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int d = 0; d < D && d < 4; ++d) m4[d] = mm[d];
+        reinterpret_cast<uint2*>(q + nb)[o] = we_pack(m4, D < 4 ? D : 3, h);
+      } else {
+        reinterpret_cast<uint32_t*>(q + nb)[o] = (e << 16) | (uint32_t)h;
+      }
+      if (last) {
+        if (!REWALK) {
+#pragma unroll
+          for (int d = 0; d < K - 1; ++d) S.flags[mm[d]] = 3;
+          S.flags[h] = 3;
+        }
+        reinterpret_cast<uint16_t*>(q + nb + ES * (int)nN)[o] = 0;
+      }
+    };
+    int64_t nN;
+    if (bfs_one_trip(K, NT, ONE_LEVELS) && nD <= NT) {
+      // One trip: thread e holds entry e.  Its count, mask, prefix members and segment bounds
+      // stay in registers from the count to the fill; the offsets come from a one-barrier scan
+      // (no MK / CN round trip, no second prefix walk; the capacity above still reserves the
+      // temps, so the same levels overflow as in the general form).  Same entry order: offset =
+      // exclusive prefix in entry order, children in list order.
+      const bool act = tid < (int)nD;
+      int mm[K] = {};
+      int lo = 0, hi = 0;
+      uint32_t mask = 0, cnt = 0;
+      typename EP::CT mc[K > 2 ? K - 2 : 1] = {};
+      if (act) {
+        prefix(q, lvl, (uint32_t)tid, mm);
+        const int m = mm[D - 1];
+        lo = S.eb(m);
+        hi = seg_end<REWALK>(S, pp, m);
+#pragma unroll
+        for (int d = 0; d < D - 1; ++d) mc[d] = ep.pt(S, mm[d]);
+        for (int t = lo; t < hi; ++t) {
+          const int h = S.dst[t];
+          const typename EP::CT ch = ep.pt(S, h);
+          bool ok = true;
+#pragma unroll
+          for (int d = 0; d < D - 1; ++d) ok &= ep.edge(mc[d], ch);
+          cnt += ok ? 1u : 0u;
+          mask |= (ok && t - lo < 32) ? (1u << (t - lo)) : 0u;
+        }
+      }
+      int tot;
+      uint32_t o = (uint32_t)block_excl_scan_add32<NT>((int)cnt, bfs_scan_slots(H), &tot);
+      nN = ufl(tot);
+      if (!next_fits(nN)) {
+        __syncthreads();   // the scan slots are read: the caller's next attempt may write them
+        return out;
+      }
       for (int t = lo; t < hi; ++t) {
         const int h = S.dst[t];
         bool ok;
@@ -877,26 +930,67 @@ struct BfsLevel {
           const typename EP::CT ch = ep.pt(S, h);
           ok = true;
 #pragma unroll
-          for (int d = 0; d < D - 1; ++d) ok &= ep.edge(ep.pt(S, mm[d]), ch);
+          for (int d = 0; d < D - 1; ++d) ok &= ep.edge(mc[d], ch);
         }
         if (!ok) continue;
-        if constexpr (WE) {
-          int m4[4] = {0, 0, 0, 0};
-#pragma unroll
-          for (int d = 0; d < D && d < 4; ++d) m4[d] = mm[d];
-          reinterpret_cast<uint2*>(q + nb)[o] = we_pack(m4, D < 4 ? D : 3, h);
-        } else {
-          reinterpret_cast<uint32_t*>(q + nb)[o] = ((uint32_t)e << 16) | (uint32_t)h;
-        }
-        if (last) {
-          if (!REWALK) {
-#pragma unroll
-            for (int d = 0; d < K - 1; ++d) S.flags[mm[d]] = 3;
-            S.flags[h] = 3;
-          }
-          reinterpret_cast<uint16_t*>(q + nb + ES * (int)nN)[o] = 0;
-        }
+        put((uint32_t)tid, mm, h, o, nN);
         ++o;
+      }
+    } else {
+      uint32_t* MK = reinterpret_cast<uint32_t*>(q + tb);
+      uint32_t* CN = MK + nD;
+      for (int e = tid; e < nD; e += NT) {
+        int mm[K];
+        prefix(q, lvl, (uint32_t)e, mm);
+        const int m = mm[D - 1];
+        const int lo = S.eb(m), hi = seg_end<REWALK>(S, pp, m);
+        uint32_t mask = 0, cnt = 0;
+        // an extension h (picker D) must be adjacent to every earlier member: the graph's edges
+        // are exactly the pairs of different pickers with JI > 0.3, so instead of a binary
+        // search of h in each member's sorted list (three dependent LDS loads each), P2's own
+        // test on the two boxes' coordinates decides it (ep.edge: the same function on the same
+        // LDS values, so the same answer); the members' coordinates stay in registers
+        typename EP::CT mc[K > 2 ? K - 2 : 1];
+  #pragma unroll
+        for (int d = 0; d < D - 1; ++d) mc[d] = ep.pt(S, mm[d]);
+        for (int t = lo; t < hi; ++t) {
+          const int h = S.dst[t];
+          const typename EP::CT ch = ep.pt(S, h);
+          bool ok = true;
+  #pragma unroll
+          for (int d = 0; d < D - 1; ++d) ok &= ep.edge(mc[d], ch);
+          cnt += ok ? 1u : 0u;
+          mask |= (ok && t - lo < 32) ? (1u << (t - lo)) : 0u;
+        }
+        MK[e] = mask;
+        CN[e] = cnt;
+      }
+      __syncthreads();
+      // (32-bit scan: nD <= 65535 entries of at most n <= 4608 extensions each, < 2^31)
+      nN = ufl(block_scan_dpp32<NT>(CN, (int)nD, H.redi));
+      if (!next_fits(nN)) return out;
+      for (int e = tid; e < nD; e += NT) {
+        int mm[K];
+        prefix(q, lvl, (uint32_t)e, mm);
+        const int m = mm[D - 1];
+        const int lo = S.eb(m), hi = seg_end<REWALK>(S, pp, m);
+        const uint32_t mask = MK[e];
+        uint32_t o = CN[e];
+        for (int t = lo; t < hi; ++t) {
+          const int h = S.dst[t];
+          bool ok;
+          if (t - lo < 32) {
+            ok = (mask >> (t - lo)) & 1u;
+          } else {
+            const typename EP::CT ch = ep.pt(S, h);
+            ok = true;
+  #pragma unroll
+            for (int d = 0; d < D - 1; ++d) ok &= ep.edge(ep.pt(S, mm[d]), ch);
+          }
+          if (!ok) continue;
+          put((uint32_t)e, mm, h, o, nN);
+          ++o;
+        }
       }
     }
     __syncthreads();
@@ -934,25 +1028,19 @@ __device__ __forceinline__ BfsOut<K> bfs_cliques(const FShared& S, FusedHdr& H, 
   };
   // level 1 -> 2: every root's first segment (picker-1 neighbours), no checks needed
   uint32_t* cnt = S.cnt;
-  for (int i = tid; i < nr; i += NT) {
-    const int r = r0 + i;
-    cnt[i] = root_ok(r) ? (uint32_t)(seg_end(r) - S.eb(r)) : 0u;
-  }
-  __syncthreads();
-  const int64_t n2 = ufl(block_scan_dpp32<NT>(cnt, nr, H.redi));   // (< n^2 < 2^31)
   constexpr bool last = K == 2;
   constexpr int ES = bfs_es<WE>();
-  if (K >= 4) out.fit = fminf(bfs_fit(n2, 65535), bfs_fit(n2 * (last ? ES + 2 : ES), qbytes));
-  if (n2 > 65535 || n2 * (last ? ES + 2 : ES) > qbytes) {
-    out.fit = fminf(out.fit, 0.999f);
-    return out;
-  }
-  for (int i = tid; i < nr; i += NT) {
-    const int r = r0 + i;
-    if (!root_ok(r)) continue;
-    uint32_t o = cnt[i];
-    const int se = seg_end(r);
-    for (int t = S.eb(r); t < se; ++t, ++o) {
+  auto level2_fits = [&](int64_t n2) {
+    if (K >= 4) out.fit = fminf(bfs_fit(n2, 65535), bfs_fit(n2 * (last ? ES + 2 : ES), qbytes));
+    if (n2 > 65535 || n2 * (last ? ES + 2 : ES) > qbytes) {
+      out.fit = fminf(out.fit, 0.999f);
+      return false;
+    }
+    return true;
+  };
+  // the level-2 entries of root r, its first segment dst[lo, hi), from index o
+  auto put = [&](int r, int lo, int hi, uint32_t o, int64_t n2) {
+    for (int t = lo; t < hi; ++t, ++o) {
       const int h = S.dst[t];
       if constexpr (WE) reinterpret_cast<uint2*>(q)[o] = make_uint2((uint32_t)r | ((uint32_t)h << 16), 0u);
       else reinterpret_cast<uint32_t*>(q)[o] = ((uint32_t)r << 16) | (uint32_t)h;
@@ -963,6 +1051,39 @@ __device__ __forceinline__ BfsOut<K> bfs_cliques(const FShared& S, FusedHdr& H, 
         }
         reinterpret_cast<uint16_t*>(q + ES * (int)n2)[o] = 0;
       }
+    }
+  };
+  int64_t n2;
+  if (bfs_one_trip(K, NT, ONE_ROOTS) && nr <= NT) {
+    // one trip (see bfs_one_trip): thread i holds root r0 + i and its segment bounds; cnt is
+    // not written (nothing reads it behind a BFS: the chunk table sits past its n0 entries
+    // and the DFS fallback fills it itself)
+    const int r = r0 + tid;
+    int lo = 0, hi = 0;
+    if (tid < nr && root_ok(r)) {
+      lo = S.eb(r);
+      hi = seg_end(r);
+    }
+    int tot;
+    const uint32_t o = (uint32_t)block_excl_scan_add32<NT>(hi - lo, bfs_scan_slots(H), &tot);
+    n2 = ufl(tot);   // (< n^2 < 2^31)
+    if (!level2_fits(n2)) {
+      __syncthreads();   // the scan slots are read: the caller's next attempt may write them
+      return out;
+    }
+    put(r, lo, hi, o, n2);
+  } else {
+    for (int i = tid; i < nr; i += NT) {
+      const int r = r0 + i;
+      cnt[i] = root_ok(r) ? (uint32_t)(seg_end(r) - S.eb(r)) : 0u;
+    }
+    __syncthreads();
+    n2 = ufl(block_scan_dpp32<NT>(cnt, nr, H.redi));   // (< n^2 < 2^31)
+    if (!level2_fits(n2)) return out;
+    for (int i = tid; i < nr; i += NT) {
+      const int r = r0 + i;
+      if (!root_ok(r)) continue;
+      put(r, S.eb(r), seg_end(r), cnt[i], n2);
     }
   }
   __syncthreads();
@@ -1849,7 +1970,11 @@ void k_fused(FusedArgs A) {
   });
   __syncthreads();
   auto cc_size = [&](uint32_t r) { return (int)((ccsz[r >> 1] >> (16 * (r & 1))) & 0xFFFF); };
-  int nodes, cc_max;
+  const bool get_cc = (A.flags & 1) != 0;
+  int nodes = 0, cc_max = 0;
+  // per-wave partials in redd: no scan of P4 uses it (the one-trip scans red64, the general
+  // form redi), so they survive until they are read
+  int* const sred = reinterpret_cast<int*>(H.redd);
   {
     // nodes and roots packed in one 64-bit sum, the largest size in one max; every thread
     // reads the per-wave partials (no thread-0 section and second barrier)
@@ -1873,22 +1998,31 @@ void k_fused(FusedArgs A) {
     });
     nr = wave_incl_add32(nr);
     mx = wave_incl_max32(mx);
-    if ((tid & 63) == 63) { H.redi[tid >> 6] = nr; reinterpret_cast<int*>(H.redu)[tid >> 6] = mx; }
-    __syncthreads();
+    if ((tid & 63) == 63) { sred[tid >> 6] = nr; sred[MAXW + (tid >> 6)] = mx; }
+  }
+  // the per-wave partials of the stats, once a barrier is behind them
+  auto cc_stats = [&]() {
     int t = 0;
     int m2 = 0;
 #pragma unroll
     for (int w = 0; w < FNW; ++w) {
-      t += H.redi[w];
-      m2 = max(m2, reinterpret_cast<const int*>(H.redu)[w]);
+      t += sred[w];
+      m2 = max(m2, sred[MAXW + w]);
     }
     nodes = t >> 16;
     cc_max = m2;
     if (tid == 0) { H.nodes = nodes; H.cc_cnt = t & 0xFFFF; H.cc_max = cc_max; }
+  };
+  // --get_cc needs cc_max at once.  Without it the stats are first needed behind P4 (set_order,
+  // put_stats): they are summed there, behind the barriers P4 takes anyway (at least one on
+  // every path), and this one goes (fused_bars).
+  const bool stats_late = (fused_bars() & BAR_P3B_STATS) != 0 && !get_cc;
+  if (!stats_late) {
+    __syncthreads();
+    cc_stats();
   }
   // (no barrier: the P4 passes below start with their own before touching the reduction
   // slots, and no array read here is written before it)
-  const bool get_cc = (A.flags & 1) != 0;
   int target = -1;
   if (get_cc) {
     // largest CC; ties -> the component whose first edge comes first in the enumeration
@@ -1925,7 +2059,6 @@ void k_fused(FusedArgs A) {
   STAMP(7);   // CC stats
   // ---- P4: k-cliques (level-synchronous BFS into the queue region; per-root DFS counts as the
   // fallback when a level does not fit), vertex marking, output reservation
-  c.set_order = 2 * K < nodes;
   const int n0 = c.pp[1];   // roots: picker-0 positions
   // queue region: after the E used entries of dst through the cell starts (contiguous: dst
   // immediately precedes the cell starts in the layout)
@@ -2016,6 +2149,8 @@ void k_fused(FusedArgs A) {
     c.cq_ord = S.cbuf + (size_t)c.cq_cap * K;
   }
   c.S.cbuf = S.cbuf;
+  if (stats_late) cc_stats();
+  c.set_order = 2 * K < nodes;
   STAMP(8);   // cliques
 #ifdef RGC_STAMPS
   if (tid == 0) {   // diagnostic build: root chunks of the BFS (0 = DFS fallback) and cliques
@@ -2041,6 +2176,11 @@ void k_fused(FusedArgs A) {
       resv = atomicAdd(A.cursor + vz, (unsigned long long)C);
     }
   }
+  // P5's bucket counters (packed u16 in the dead union-find parents, read for the last time
+  // before the barriers of P4's own passes) are zeroed in front of this barrier, so P5 opens
+  // without one of its own
+  if (fused_bars() & BAR_P5_ZERO)
+    for (int q = tid; q <= (n + 1) / 2; q += FWG) reinterpret_cast<uint32_t*>(S.parent)[q] = 0;
   __syncthreads();
 
   STOP_AFTER(4);
@@ -2062,8 +2202,10 @@ void k_fused(FusedArgs A) {
     auto ld = [&](int t) -> CT2 { return reinterpret_cast<const CT2*>(S.sxy)[t]; };
     const CT minx = (CT)H.minx, xbs = (CT)H.xbs, nlast = (CT)(n - 1);
     auto xbucket = [&](CT xv) { return (int)fmin((xv - minx) * xbs, nlast); };
-    for (int q = tid; q <= (n + 1) / 2; q += FWG) bw[q] = 0;
-    __syncthreads();
+    if (!(fused_bars() & BAR_P5_ZERO)) {
+      for (int q = tid; q <= (n + 1) / 2; q += FWG) bw[q] = 0;
+      __syncthreads();
+    }
     in_flight<NF_P5, FWG>(tid, n, [&](auto it, int first) {
       constexpr int N = decltype(it)::n;
       int f[N], q[N];
