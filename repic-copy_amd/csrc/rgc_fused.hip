@@ -59,35 +59,15 @@ constexpr int MAXW = 16;            // reduction slots: up to 1024-thread workgr
 // 1024: C3's ~4.1k boxes all stay in registers, VGPRs to spare at 4 waves per SIMD; boxes past
 // RB * NT are re-read from HBM in each of P0's and P1's passes)
 constexpr int fused_rb(int nt) { return nt <= 256 ? 4 : nt >= 1024 ? 5 : 2; }
-// Phases whose per-box / per-edge / per-vertex loops keep two items of a thread in flight
-// (in_flight).  None in the product: every phase runs its staged body one item at a time,
-// which is where the measured gain is; each pair form on top of it was inside the spread or
-// slower (profiles/r11f).  RGC_TWO_MASK selects phases for timing
-// experiments (`make xp X=M4 XDEF=-DRGC_TWO_MASK=4u`, tools/ablate.py), within what the
-// instance's registers allow without crossing an occupancy step.
-enum : unsigned { TWO_P1 = 1, TWO_P2C = 2, TWO_P3A = 4, TWO_P3B = 8, TWO_P5 = 16, TWO_P6A = 32 };
-#ifndef RGC_TWO_MASK
-#define RGC_TWO_MASK 0u
-#endif
-constexpr unsigned fused_two(int k, bool wide, int nt) {
-  unsigned m = RGC_TWO_MASK;
-  // P1 holds all RB register boxes of a thread at once: with 4 or 5 of them the 256-thread
-  // instances spill and the 1024-thread ones lose a wave per SIMD
-  if (fused_rb(nt) != 2) m &= ~TWO_P1;
-  // K >= 4: P5's two-vertex rank loop takes K = 5 / 768 threads and K = 4 / 1024 from 72 to 73
-  // VGPRs, one allocation granule up
-  if (k >= 4) m &= ~TWO_P5;
-  return m;
-}
-
-// Barriers taken off the workgroup's chain by moving work in front of one that is there anyway
-// (RGC_BAR_MASK selects them for timing experiments): P5's counter zeroing in front of P4's
-// reservation barrier; P3b's stats summed behind P4's barriers when --get_cc is off.
-enum : unsigned { BAR_P5_ZERO = 1, BAR_P3B_STATS = 2 };
-#ifndef RGC_BAR_MASK
-#define RGC_BAR_MASK 3u
-#endif
-constexpr unsigned fused_bars() { return RGC_BAR_MASK; }
+// The per-box / per-edge / per-vertex loops of P1, P2c, P3, P5 and P6a run one item of a thread
+// at a time, each iteration staged: its loads at known addresses first, then the flag test,
+// then the action.  That order is the measured gain.  Keeping two items of a thread in flight
+// on top of it was inside the spread or slower in every phase (DESIGN.md section 4,
+// profiles/r11f); those pair forms were taken out of the source and rebuild from a42a7dc.
+// Two barriers are off the workgroup's chain because their work sits in front of one that is
+// there anyway: P5's counter zeroing in front of P4's reservation barrier, and P3b's stats
+// summed behind P4's barriers when --get_cc is off (profiles/r12; the switches that timed
+// them rebuild from 25f33ec).
 
 struct FusedHdr {
   // reduction scratch: the single-value reductions alias the 4-way one (every reduction
@@ -288,7 +268,7 @@ __device__ __forceinline__ uint32_t uf_find32p(uint32_t* parent, uint32_t x, uin
   return uf_find32(parent, gp);
 }
 // union of a and b given pa, pb loaded from parent[a], parent[b]: the caller issues those loads
-// (of both endpoints, and of every edge it has in flight) together
+// (of both endpoints) together
 __device__ __forceinline__ void uf_union32p(uint32_t* parent, uint32_t a, uint32_t pa,
                                             uint32_t b, uint32_t pb) {
   a = uf_find32p(parent, a, pa);
@@ -349,68 +329,16 @@ __device__ __forceinline__ int lb16(const uint16_t* a, int lo, int hi, int v) {
   return lo;
 }
 
-// ---- several items of one thread in flight.  A per-item loop `for (i = tid; i < n; i += S)`
-// runs each item as its own chain of dependent LDS round trips, and the compiler cannot move
-// item 2's loads above item 1's stores and atomics (same address space).  The loops below are
-// written as a body over N items (i = first + j * S, j < N), each stage an `each` call over
-// all N before the next stage starts, so the N loads of a stage are issued before the first
-// wait.  in_flight runs the body with N = NI for the thread's first NI items and with N = 1 for
-// any further ones (NI = 1: the plain loop).  A wave whose lanes all hold NI items (every wave
-// of the second round but the last) runs the body without the per-item tests: their exec
-// regions would each wait for everything in flight before them.
-template <int N, int S, bool ALL>
-struct Items {
-  static constexpr int n = N;
-  // fn(j, i) for each of the N items that exists
-  template <class F>
-  __device__ __forceinline__ void each(int first, int end, F&& fn) const {
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      const int i = first + j * S;
-      if (ALL || i < end) fn(j, i);
-    }
+// lb16 with select-updated bounds: a step is a probe and two selects, no branch on the compare
+// (an empty range, lo >= hi, probes nothing and returns lo)
+__device__ __forceinline__ int lb16s(const uint16_t* a, int lo, int hi, int v) {
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    const bool up = (int)a[mid] < v;
+    lo = up ? mid + 1 : lo;
+    hi = up ? hi : mid;
   }
-};
-// (first = the lane's index in its wave + a wave-uniform multiple of 64)
-template <int N, int S>
-__device__ __forceinline__ bool wave_holds_all(int first, int n) {
-#ifdef RGC_NO_ALL   // (timing experiments: the pair forms without the full-wave path)
-  return false;
-#endif
-  return __builtin_amdgcn_readfirstlane(first & ~63) + 63 + (N - 1) * S < n;
-}
-template <int NI, int S, class Body>
-__device__ __forceinline__ void in_flight(int first, int n, Body&& body) {
-  if constexpr (NI > 1) {
-    if (wave_holds_all<NI, S>(first, n)) body(Items<NI, S, true>{}, first);
-    else body(Items<NI, S, false>{}, first);
-  }
-  for (int i = first + (NI > 1 ? NI * S : 0); i < n; i += S) body(Items<1, S, false>{}, i);
-}
-
-// lb16 for N searches at once: every step loads all N probes before the first compare (a
-// finished or empty search, lo >= hi, probes a[0] and keeps its bounds)
-template <int N>
-__device__ __forceinline__ void lb16n(const uint16_t* a, int (&lo)[N], int (&hi)[N],
-                                      const int (&v)[N]) {
-  for (;;) {
-    bool any = false;
-#pragma unroll
-    for (int j = 0; j < N; ++j) any |= lo[j] < hi[j];
-    if (!any) return;
-    int mid[N], x[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      mid[j] = (lo[j] + hi[j]) >> 1;
-      x[j] = a[lo[j] < hi[j] ? mid[j] : 0];
-    }
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      const bool act = lo[j] < hi[j], up = x[j] < v[j];
-      lo[j] = act && up ? mid[j] + 1 : lo[j];
-      hi[j] = act && !up ? mid[j] : hi[j];
-    }
-  }
+  return lo;
 }
 
 __device__ __forceinline__ bool contains16(const uint16_t* a, int lo, int hi, int v) {
@@ -787,15 +715,7 @@ __device__ __forceinline__ uint2 we_pack(const int (&mm)[4], int d, int h) {
 // (`make resources`): K = 3 / 1024 and every K = 4 instance drop an
 // occupancy step, K = 5 / 768 (f64 layout) grows its scratch and K = 5 / 768 (f32) drops a step,
 // and so on up to K = 8; they keep the general form alone.
-// RGC_BFS_ONE selects the parts for timing experiments (`make xp X=B0 XDEF=-DRGC_BFS_ONE=0`):
-// 1 the levels, 2 the root pass, 4 every instance.
-#ifndef RGC_BFS_ONE
-#define RGC_BFS_ONE 3
-#endif
-enum : int { ONE_LEVELS = 1, ONE_ROOTS = 2, ONE_EVERY = 4 };
-constexpr bool bfs_one_trip(int k, int nt, int part) {
-  return (RGC_BFS_ONE & part) != 0 && ((RGC_BFS_ONE & ONE_EVERY) != 0 || (k <= 3 && nt <= 768));
-}
+constexpr bool bfs_one_trip(int k, int nt) { return k <= 3 && nt <= 768; }
 // Per-wave slots of the one-trip scans.  Not redi / redu: P3b's stats reduction reads those
 // up to the first barrier P4 takes, which is the root pass's scan barrier.  Consecutive
 // one-trip scans are separated by the barrier behind the fill (or, on overflow, behind the
@@ -885,57 +805,75 @@ struct BfsLevel {
         reinterpret_cast<uint16_t*>(q + nb + ES * (int)nN)[o] = 0;
       }
     };
-    int64_t nN;
-    if (bfs_one_trip(K, NT, ONE_LEVELS) && nD <= NT) {
-      // One trip: thread e holds entry e.  Its count, mask, prefix members and segment bounds
-      // stay in registers from the count to the fill; the offsets come from a one-barrier scan
-      // (no MK / CN round trip, no second prefix walk; the capacity above still reserves the
-      // temps, so the same levels overflow as in the general form).  Same entry order: offset =
-      // exclusive prefix in entry order, children in list order.
-      const bool act = tid < (int)nD;
-      int mm[K] = {};
-      int lo = 0, hi = 0;
-      uint32_t mask = 0, cnt = 0;
-      typename EP::CT mc[K > 2 ? K - 2 : 1] = {};
-      if (act) {
-        prefix(q, lvl, (uint32_t)tid, mm);
-        const int m = mm[D - 1];
-        lo = S.eb(m);
-        hi = seg_end<REWALK>(S, pp, m);
+    using CT = typename EP::CT;
+    constexpr int NC = K > 2 ? K - 2 : 1;
+    // Candidate walk of an entry: count and 32-bit mask of the valid extensions among dst[lo, hi),
+    // the first segment of its last member's list.  An extension h (picker D) must be adjacent to
+    // every earlier member: the graph's edges are exactly the pairs of different pickers with
+    // JI > 0.3, so instead of a binary search of h in each member's sorted list (three dependent
+    // LDS loads each), P2's own test on the two boxes' coordinates decides it (ep.edge: the same
+    // function on the same LDS values, so the same answer); the members' coordinates mc stay in
+    // registers.
+    auto candidates = [&](int lo, int hi, const CT (&mc)[NC], uint32_t& cnt, uint32_t& mask) {
+      for (int t = lo; t < hi; ++t) {
+        const int h = S.dst[t];
+        const CT ch = ep.pt(S, h);
+        bool ok = true;
 #pragma unroll
-        for (int d = 0; d < D - 1; ++d) mc[d] = ep.pt(S, mm[d]);
-        for (int t = lo; t < hi; ++t) {
-          const int h = S.dst[t];
-          const typename EP::CT ch = ep.pt(S, h);
-          bool ok = true;
-#pragma unroll
-          for (int d = 0; d < D - 1; ++d) ok &= ep.edge(mc[d], ch);
-          cnt += ok ? 1u : 0u;
-          mask |= (ok && t - lo < 32) ? (1u << (t - lo)) : 0u;
-        }
+        for (int d = 0; d < D - 1; ++d) ok &= ep.edge(mc[d], ch);
+        cnt += ok ? 1u : 0u;
+        mask |= (ok && t - lo < 32) ? (1u << (t - lo)) : 0u;
       }
-      int tot;
-      uint32_t o = (uint32_t)block_excl_scan_add32<NT>((int)cnt, bfs_scan_slots(H), &tot);
-      nN = ufl(tot);
-      if (!next_fits(nN)) {
-        __syncthreads();   // the scan slots are read: the caller's next attempt may write them
-        return out;
-      }
+    };
+    // Fill walk of entry e (prefix mm): its valid extensions, by the mask or past the 32nd
+    // candidate by the test again (member d's coordinates from mc(d)), become the next level's
+    // entries from index o, in list order.
+    auto fill = [&](uint32_t e, const int (&mm)[K], int lo, int hi, uint32_t mask, uint32_t o,
+                    int64_t nN, auto&& mc) {
       for (int t = lo; t < hi; ++t) {
         const int h = S.dst[t];
         bool ok;
         if (t - lo < 32) {
           ok = (mask >> (t - lo)) & 1u;
         } else {
-          const typename EP::CT ch = ep.pt(S, h);
+          const CT ch = ep.pt(S, h);
           ok = true;
 #pragma unroll
-          for (int d = 0; d < D - 1; ++d) ok &= ep.edge(mc[d], ch);
+          for (int d = 0; d < D - 1; ++d) ok &= ep.edge(mc(d), ch);
         }
         if (!ok) continue;
-        put((uint32_t)tid, mm, h, o, nN);
+        put(e, mm, h, o, nN);
         ++o;
       }
+    };
+    int64_t nN;
+    if (bfs_one_trip(K, NT) && nD <= NT) {
+      // One trip: thread e holds entry e.  Its count, mask, prefix members and segment bounds
+      // stay in registers from the count to the fill; the offsets come from a one-barrier scan
+      // (no MK / CN round trip, no second prefix walk; the capacity above still reserves the
+      // temps, so the same levels overflow as in the general form).  Same entry order: offset =
+      // exclusive prefix in entry order, children in list order.
+      int mm[K] = {};
+      int lo = 0, hi = 0;
+      uint32_t mask = 0, cnt = 0;
+      CT mc[NC] = {};
+      if (tid < (int)nD) {
+        prefix(q, lvl, (uint32_t)tid, mm);
+        const int m = mm[D - 1];
+        lo = S.eb(m);
+        hi = seg_end<REWALK>(S, pp, m);
+#pragma unroll
+        for (int d = 0; d < D - 1; ++d) mc[d] = ep.pt(S, mm[d]);
+        candidates(lo, hi, mc, cnt, mask);
+      }
+      int tot;
+      const uint32_t o = (uint32_t)block_excl_scan_add32<NT>((int)cnt, bfs_scan_slots(H), &tot);
+      nN = ufl(tot);
+      if (!next_fits(nN)) {
+        __syncthreads();   // the scan slots are read: the caller's next attempt may write them
+        return out;
+      }
+      fill((uint32_t)tid, mm, lo, hi, mask, o, nN, [&](int d) { return mc[d]; });
     } else {
       uint32_t* MK = reinterpret_cast<uint32_t*>(q + tb);
       uint32_t* CN = MK + nD;
@@ -945,23 +883,10 @@ struct BfsLevel {
         const int m = mm[D - 1];
         const int lo = S.eb(m), hi = seg_end<REWALK>(S, pp, m);
         uint32_t mask = 0, cnt = 0;
-        // an extension h (picker D) must be adjacent to every earlier member: the graph's edges
-        // are exactly the pairs of different pickers with JI > 0.3, so instead of a binary
-        // search of h in each member's sorted list (three dependent LDS loads each), P2's own
-        // test on the two boxes' coordinates decides it (ep.edge: the same function on the same
-        // LDS values, so the same answer); the members' coordinates stay in registers
-        typename EP::CT mc[K > 2 ? K - 2 : 1];
-  #pragma unroll
+        CT mc[NC];
+#pragma unroll
         for (int d = 0; d < D - 1; ++d) mc[d] = ep.pt(S, mm[d]);
-        for (int t = lo; t < hi; ++t) {
-          const int h = S.dst[t];
-          const typename EP::CT ch = ep.pt(S, h);
-          bool ok = true;
-  #pragma unroll
-          for (int d = 0; d < D - 1; ++d) ok &= ep.edge(mc[d], ch);
-          cnt += ok ? 1u : 0u;
-          mask |= (ok && t - lo < 32) ? (1u << (t - lo)) : 0u;
-        }
+        candidates(lo, hi, mc, cnt, mask);
         MK[e] = mask;
         CN[e] = cnt;
       }
@@ -973,24 +898,10 @@ struct BfsLevel {
         int mm[K];
         prefix(q, lvl, (uint32_t)e, mm);
         const int m = mm[D - 1];
-        const int lo = S.eb(m), hi = seg_end<REWALK>(S, pp, m);
-        const uint32_t mask = MK[e];
-        uint32_t o = CN[e];
-        for (int t = lo; t < hi; ++t) {
-          const int h = S.dst[t];
-          bool ok;
-          if (t - lo < 32) {
-            ok = (mask >> (t - lo)) & 1u;
-          } else {
-            const typename EP::CT ch = ep.pt(S, h);
-            ok = true;
-  #pragma unroll
-            for (int d = 0; d < D - 1; ++d) ok &= ep.edge(ep.pt(S, mm[d]), ch);
-          }
-          if (!ok) continue;
-          put((uint32_t)e, mm, h, o, nN);
-          ++o;
-        }
+        // (the members' coordinates are not held across this walk: read where a list passes 32
+        // candidates, which is rare)
+        fill((uint32_t)e, mm, S.eb(m), seg_end<REWALK>(S, pp, m), MK[e], CN[e], nN,
+             [&](int d) { return ep.pt(S, mm[d]); });
       }
     }
     __syncthreads();
@@ -1054,7 +965,7 @@ __device__ __forceinline__ BfsOut<K> bfs_cliques(const FShared& S, FusedHdr& H, 
     }
   };
   int64_t n2;
-  if (bfs_one_trip(K, NT, ONE_ROOTS) && nr <= NT) {
+  if (bfs_one_trip(K, NT) && nr <= NT) {
     // one trip (see bfs_one_trip): thread i holds root r0 + i and its segment bounds; cnt is
     // not written (nothing reads it behind a BFS: the chunk table sits past its n0 entries
     // and the DFS fallback fills it itself)
@@ -1536,29 +1447,6 @@ void k_fused(FusedArgs A) {
     }
     for (int i = tid + RB * FWG; i < n; i += FWG) fn(i, ax[b0 + i], ay[b0 + i]);
   };
-  // the staged form (in_flight): body(Items<N, ..>, first, xy) with xy(j, i) the coordinates of
-  // item j; the RB register boxes of a thread run as one body when TWO
-  constexpr unsigned TWOM = fused_two(K, W, NT);
-  constexpr bool TWO = (TWOM & TWO_P1) != 0;
-  // items in flight of each phase's loops over positions, edges or vertices
-  constexpr int NF_P2C = TWOM & TWO_P2C ? 2 : 1, NF_P3A = TWOM & TWO_P3A ? 2 : 1,
-                NF_P3B = TWOM & TWO_P3B ? 2 : 1, NF_P5 = TWOM & TWO_P5 ? 2 : 1,
-                NF_P6A = TWOM & TWO_P6A ? 2 : 1;
-  auto each_box_staged = [&](auto&& body) {
-    if constexpr (TWO) {
-      auto xy = [&](int j, int) { return make_double2(rx[j], ry[j]); };
-      if (wave_holds_all<RB, FWG>(tid, n)) body(Items<RB, FWG, true>{}, tid, xy);
-      else body(Items<RB, FWG, false>{}, tid, xy);
-    } else {
-#pragma unroll
-      for (int j = 0; j < RB; ++j)
-        body(Items<1, FWG, false>{}, tid + j * FWG,
-             [&](int, int) { return make_double2(rx[j], ry[j]); });
-    }
-    for (int i = tid + RB * FWG; i < n; i += FWG)
-      body(Items<1, FWG, false>{}, i,
-           [&](int, int ii) { return make_double2(ax[b0 + ii], ay[b0 + ii]); });
-  };
   // bounding box on floats for the f32 layout (exact there; a micrograph with inexact
   // coordinates is deferred to the f64 layout, where it is computed in f64)
   using BT = typename std::conditional<W, double, float>::type;
@@ -1695,48 +1583,39 @@ void k_fused(FusedArgs A) {
   block_scan_dpp32<FWG>(S.cstart, nk + 2, H.redi);
   // arrival order into fwd (free until P2), made deterministic by the placement pass
   uint16_t* arrival = S.fwd;
-  each_box_staged([&](auto it, int first, auto&&) {
-    constexpr int N = decltype(it)::n;
-    int q[N];
-    uint32_t t[N];
-    it.each(first, n, [&](int j, int i) { q[j] = S.pos[i]; });
-    it.each(first, n, [&](int j, int) {
-      t[j] = atomicAdd(&cw[q[j] >> 1], 1u << (16 * (q[j] & 1)));
-    });
-    it.each(first, n, [&](int j, int i) {
-      arrival[(t[j] >> (16 * (q[j] & 1))) & 0xFFFF] = (uint16_t)i;
-    });
+  each_box([&](int i, double, double) {
+    const int q = S.pos[i];
+    const uint32_t t = atomicAdd(&cw[q >> 1], 1u << (16 * (q & 1)));
+    arrival[(t >> (16 * (q & 1))) & 0xFFFF] = (uint16_t)i;
   });
   __syncthreads();
-  // placement: by local index inside each bucket (buckets hold a few boxes; the items' buckets
-  // are walked in one loop over the longest, a shorter one re-reading its first entry)
-  each_box_staged([&](auto it, int first, auto&& xy) {
-    constexpr int N = decltype(it)::n;
-    int q[N], lo[N] = {}, len[N] = {}, t[N];
-    it.each(first, n, [&](int j, int i) { q[j] = S.pos[i]; });
-    it.each(first, n, [&](int j, int) {
-      lo[j] = S.cstart[q[j] - 1];
-      len[j] = (int)S.cstart[q[j]] - lo[j];
-    });
-    int ml = 0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) { ml = max(ml, len[j]); t[j] = lo[j]; }
-#pragma nounroll
-    for (int u = 0; u < ml; ++u) {
-      int a[N];
-#pragma unroll
-      for (int j = 0; j < N; ++j) a[j] = arrival[lo[j] + (u < len[j] ? u : 0)];
-#pragma unroll
-      for (int j = 0; j < N; ++j) t[j] += (u < len[j] && a[j] < first + j * FWG) ? 1 : 0;
+  // placement: by local index inside each bucket (buckets hold a few boxes).  Written per
+  // box, not through each_box: each stage tests i < n on its own and the walk stands outside
+  // those tests (a thread without the box walks an empty bucket).  With the whole body under
+  // one test the compiler fuses the two bounds into one 32-bit LDS read at a 2-byte-aligned
+  // address and the 1024-thread K = 4 instance needs another register.
+  auto place = [&](int i, auto&& xy) {
+    int q = 0, lo = 0, len = 0;
+    if (i < n) q = S.pos[i];
+    if (i < n) {
+      lo = S.cstart[q - 1];
+      len = (int)S.cstart[q] - lo;
     }
-    it.each(first, n, [&](int j, int i) {
-      const double2 v = xy(j, i);
-      S.scell[t[j]] = (uint16_t)(q[j] - 1);
-      S.citems[t[j]] = (uint16_t)i;
-      S.pos[i] = (uint16_t)t[j];
-      st_xy<W>(S, t[j], v.x, v.y);
-    });
-  });
+    int t = lo;
+#pragma nounroll
+    for (int u = 0; u < len; ++u) t += (int)arrival[lo + u] < i ? 1 : 0;
+    if (i < n) {
+      const double2 v = xy();
+      S.scell[t] = (uint16_t)(q - 1);
+      S.citems[t] = (uint16_t)i;
+      S.pos[i] = (uint16_t)t;
+      st_xy<W>(S, t, v.x, v.y);
+    }
+  };
+#pragma unroll
+  for (int j = 0; j < RB; ++j) place(tid + j * FWG, [&]() { return make_double2(rx[j], ry[j]); });
+  for (int i = tid + RB * FWG; i < n; i += FWG)
+    place(i, [&]() { return make_double2(ax[b0 + i], ay[b0 + i]); });
   __syncthreads();
   // picker bounds in position space: grid p occupies [pp[p], pp[p+1]); non-finite boxes follow
 #pragma unroll
@@ -1853,28 +1732,22 @@ void k_fused(FusedArgs A) {
     // (QG: esrc_g in HBM when dst's tail is short; separate loops keep esrc's LDS accesses
     // ds_* instructions instead of flat ones)
     {
-      in_flight<NF_P2C, FWG>(tid, n, [&](auto it, int first) {
-        constexpr int N = decltype(it)::n;
-        int base[N], cnt[N];
-        it.each(first, n, [&](int j, int i) {
-          base[j] = S.eb(i);
-          cnt[j] = S.ee(i) - base[j];
-        });
-        it.each(first, n, [&](int j, int i) {
-          if (src_hbm) {
-            for (int e = 0; e < cnt[j]; ++e) esrc_g[base[j] + e] = (uint16_t)i;
-          } else if (src_ok) {
-            for (int e = 0; e < cnt[j]; ++e) esrc[base[j] + e] = (uint16_t)i;
-          } else {
-            const uint16_t* d = S.dst + base[j];
-            for (int e = 0; e < cnt[j]; ++e) {
-              S.flags[d[e]] = 1;
-              uf_union_lds(S.parent, (uint32_t)i, (uint32_t)d[e]);
-            }
+      for (int i = tid; i < n; i += FWG) {
+        const int base = S.eb(i);
+        const int cnt = S.ee(i) - base;
+        if (src_hbm) {
+          for (int e = 0; e < cnt; ++e) esrc_g[base + e] = (uint16_t)i;
+        } else if (src_ok) {
+          for (int e = 0; e < cnt; ++e) esrc[base + e] = (uint16_t)i;
+        } else {
+          const uint16_t* d = S.dst + base;
+          for (int e = 0; e < cnt; ++e) {
+            S.flags[d[e]] = 1;
+            uf_union_lds(S.parent, (uint32_t)i, (uint32_t)d[e]);
           }
-          if (src_ok) S.cnt[i] = (uint32_t)i;
-        });
-      });
+        }
+        if (src_ok) S.cnt[i] = (uint32_t)i;
+      }
       __syncthreads();
     }
     STAMP(5);   // edge sources (or per-box unions) and identity parents
@@ -1900,19 +1773,13 @@ void k_fused(FusedArgs A) {
       }
       __syncthreads();
     } else if (src_ok) {
-      in_flight<NF_P3A, FWG>(tid, E, [&](auto it, int first) {
-        constexpr int N = decltype(it)::n;
-        uint32_t a[N], h[N], pa[N], ph[N];
-        it.each(first, E, [&](int j, int e) { a[j] = esrc[e]; h[j] = S.dst[e]; });
-        it.each(first, E, [&](int j, int) {
-          pa[j] = lds_ld(S.cnt + a[j]);
-          ph[j] = lds_ld(S.cnt + h[j]);
-        });
-        it.each(first, E, [&](int j, int) {
-          S.flags[h[j]] = 1;
-          uf_union32p(S.cnt, a[j], pa[j], h[j], ph[j]);
-        });
-      });
+      // both endpoints, then both parents, are loaded before the flag store and either find
+      for (int e = tid; e < E; e += FWG) {
+        const uint32_t a = esrc[e], h = S.dst[e];
+        const uint32_t pa = lds_ld(S.cnt + a), ph = lds_ld(S.cnt + h);
+        S.flags[h] = 1;
+        uf_union32p(S.cnt, a, pa, h, ph);
+      }
       __syncthreads();
     }
     cc32 = src_ok;
@@ -1946,28 +1813,20 @@ void k_fused(FusedArgs A) {
   
   // ---- P3: connected components: the unions ran in the P2 fill; compress, count sizes
   STAMP(6);   // union (one thread per edge)
-  in_flight<NF_P3B, FWG>(tid, n, [&](auto it, int first) {
-    constexpr int N = decltype(it)::n;
-    int f[N] = {}, lo[N] = {}, hi[N] = {}, v[N] = {};
-    uint32_t p[N];
-    it.each(first, n, [&](int j, int i) {
-      f[j] = S.flags[i];
-      lo[j] = S.eb(i);
-      hi[j] = S.ee(i);
-      if (cc32) p[j] = lds_ld(S.cnt + i);
-      v[j] = next_picker_end<K>(c.pp, i);
-    });
-#pragma unroll
-    for (int j = 0; j < N; ++j) hi[j] = f[j] ? hi[j] : lo[j];
-    lb16n<N>(S.dst, lo, hi, v);
-    it.each(first, n, [&](int j, int i) {
-      if (!f[j]) return;
-      S.split[i] = (uint16_t)lo[j];   // every node
-      const uint32_t r = cc32 ? uf_find32p(S.cnt, i, p[j]) : uf_find_lds(S.parent, i);
-      p16_st(S.parent + i, r);
-      atomicAdd(&ccsz[r >> 1], 1u << (16 * (r & 1)));
-    });
-  });
+  // the flag, the list bounds and the parent are loaded together, before the flag is tested: a
+  // box that is no node searches an empty range
+  for (int i = tid; i < n; i += FWG) {
+    const int f = S.flags[i];
+    const int lo = S.eb(i), hi = S.ee(i);
+    uint32_t p = 0;
+    if (cc32) p = lds_ld(S.cnt + i);
+    const int sp = lb16s(S.dst, lo, f ? hi : lo, next_picker_end<K>(c.pp, i));
+    if (!f) continue;
+    S.split[i] = (uint16_t)sp;   // every node
+    const uint32_t r = cc32 ? uf_find32p(S.cnt, i, p) : uf_find_lds(S.parent, i);
+    p16_st(S.parent + i, r);
+    atomicAdd(&ccsz[r >> 1], 1u << (16 * (r & 1)));
+  }
   __syncthreads();
   auto cc_size = [&](uint32_t r) { return (int)((ccsz[r >> 1] >> (16 * (r & 1))) & 0xFFFF); };
   const bool get_cc = (A.flags & 1) != 0;
@@ -1981,21 +1840,13 @@ void k_fused(FusedArgs A) {
     // nodes << 16 | roots (both <= n < 2^16) in one 32-bit sum
     int nr = 0;
     int mx = 0;
-    in_flight<NF_P3B, FWG>(tid, n, [&](auto it, int first) {
-      constexpr int N = decltype(it)::n;
-      int f[N], p[N];
-      uint32_t sz[N];
-      it.each(first, n, [&](int j, int i) {
-        f[j] = S.flags[i];
-        p[j] = S.parent[i];
-        sz[j] = ccsz[i >> 1];
-      });
-      it.each(first, n, [&](int j, int i) {
-        if (!f[j]) return;
-        nr += 1 << 16;
-        if (p[j] == i) { nr += 1; mx = max(mx, (int)((sz[j] >> (16 * (i & 1))) & 0xFFFF)); }
-      });
-    });
+    for (int i = tid; i < n; i += FWG) {
+      const int f = S.flags[i], p = S.parent[i];
+      const uint32_t sz = ccsz[i >> 1];
+      if (!f) continue;
+      nr += 1 << 16;
+      if (p == i) { nr += 1; mx = max(mx, (int)((sz >> (16 * (i & 1))) & 0xFFFF)); }
+    }
     nr = wave_incl_add32(nr);
     mx = wave_incl_max32(mx);
     if ((tid & 63) == 63) { sred[tid >> 6] = nr; sred[MAXW + (tid >> 6)] = mx; }
@@ -2015,8 +1866,8 @@ void k_fused(FusedArgs A) {
   };
   // --get_cc needs cc_max at once.  Without it the stats are first needed behind P4 (set_order,
   // put_stats): they are summed there, behind the barriers P4 takes anyway (at least one on
-  // every path), and this one goes (fused_bars).
-  const bool stats_late = (fused_bars() & BAR_P3B_STATS) != 0 && !get_cc;
+  // every path), and this one goes.
+  const bool stats_late = !get_cc;
   if (!stats_late) {
     __syncthreads();
     cc_stats();
@@ -2179,8 +2030,7 @@ void k_fused(FusedArgs A) {
   // P5's bucket counters (packed u16 in the dead union-find parents, read for the last time
   // before the barriers of P4's own passes) are zeroed in front of this barrier, so P5 opens
   // without one of its own
-  if (fused_bars() & BAR_P5_ZERO)
-    for (int q = tid; q <= (n + 1) / 2; q += FWG) reinterpret_cast<uint32_t*>(S.parent)[q] = 0;
+  for (int q = tid; q <= (n + 1) / 2; q += FWG) reinterpret_cast<uint32_t*>(S.parent)[q] = 0;
   __syncthreads();
 
   STOP_AFTER(4);
@@ -2202,77 +2052,46 @@ void k_fused(FusedArgs A) {
     auto ld = [&](int t) -> CT2 { return reinterpret_cast<const CT2*>(S.sxy)[t]; };
     const CT minx = (CT)H.minx, xbs = (CT)H.xbs, nlast = (CT)(n - 1);
     auto xbucket = [&](CT xv) { return (int)fmin((xv - minx) * xbs, nlast); };
-    if (!(fused_bars() & BAR_P5_ZERO)) {
-      for (int q = tid; q <= (n + 1) / 2; q += FWG) bw[q] = 0;
-      __syncthreads();
+    // count: the vertex's ordinal within its bucket waits in vrank (flag and x loaded together,
+    // before the flag is tested)
+    for (int t = tid; t < n; t += FWG) {
+      const int f = S.flags[t];
+      const CT x = ld(t).x;
+      if (f != 3) continue;
+      const int q = xbucket(x);
+      const uint32_t r = atomicAdd(&bw[q >> 1], 1u << (16 * (q & 1)));
+      S.vrank[t] = (uint16_t)((r >> (16 * (q & 1))) & 0xFFFFu);
     }
-    in_flight<NF_P5, FWG>(tid, n, [&](auto it, int first) {
-      constexpr int N = decltype(it)::n;
-      int f[N], q[N];
-      uint32_t r[N];
-      CT x[N];
-      it.each(first, n, [&](int j, int t) { f[j] = S.flags[t]; x[j] = ld(t).x; });
-      it.each(first, n, [&](int j, int) {
-        if (f[j] != 3) return;
-        q[j] = xbucket(x[j]);
-        r[j] = atomicAdd(&bw[q[j] >> 1], 1u << (16 * (q[j] & 1)));
-      });
-      it.each(first, n, [&](int j, int t) {
-        if (f[j] == 3) S.vrank[t] = (uint16_t)((r[j] >> (16 * (q[j] & 1))) & 0xFFFFu);
-      });
-    });
     __syncthreads();
     const int V = block_scan_dpp32<FWG>(bcnt, n, H.redi);
     if (tid == 0) { H.V = (int)V; bcnt[n] = (uint16_t)V; }
-    in_flight<NF_P5, FWG>(tid, n, [&](auto it, int first) {
-      constexpr int N = decltype(it)::n;
-      int f[N], vr[N], bb[N];
-      CT x[N];
-      it.each(first, n, [&](int j, int t) {
-        f[j] = S.flags[t];
-        x[j] = ld(t).x;
-        vr[j] = S.vrank[t];
-      });
-      it.each(first, n, [&](int j, int) { if (f[j] == 3) bb[j] = bcnt[xbucket(x[j])]; });
-      it.each(first, n, [&](int j, int t) {
-        if (f[j] == 3) blist[bb[j] + vr[j]] = (uint16_t)t;
-      });
-    });
+    for (int t = tid; t < n; t += FWG) {
+      const int f = S.flags[t];
+      const CT x = ld(t).x;
+      const int vr = S.vrank[t];
+      if (f != 3) continue;
+      blist[bcnt[xbucket(x)] + vr] = (uint16_t)t;
+    }
     __syncthreads();
     // ranks over the dense bucket-ordered vertex list (every lane holds a vertex; the
-    // position loop above skips the non-vertices).  The items' buckets are walked in one loop
-    // over the longest, a shorter one re-reading its first entry.
-    in_flight<NF_P5, FWG>(tid, V, [&](auto it, int first) {
-      constexpr int N = decltype(it)::n;
-      int t[N] = {}, vi[N] = {}, lo[N] = {}, len[N] = {};
-      CT2 v[N] = {};
-      uint32_t rk[N];
-      it.each(first, V, [&](int j, int u0) { t[j] = blist[u0]; });
-      it.each(first, V, [&](int j, int) { vi[j] = S.citems[t[j]]; v[j] = ld(t[j]); });
-      it.each(first, V, [&](int j, int) {
-        const int b = xbucket(v[j].x);
-        lo[j] = bcnt[b];
-        len[j] = (int)bcnt[b + 1] - lo[j];
-      });
-      int ml = 0;
-#pragma unroll
-      for (int j = 0; j < N; ++j) { ml = max(ml, len[j]); rk[j] = lo[j]; }
+    // position loop above skips the non-vertices)
+    for (int u0 = tid; u0 < V; u0 += FWG) {
+      const int t = blist[u0];
+      const int vi = S.citems[t];
+      const CT2 v = ld(t);
+      const int b = xbucket(v.x);
+      const int lo = bcnt[b];
+      const int len = (int)bcnt[b + 1] - lo;
+      uint32_t rk = lo;
 #pragma nounroll
-      for (int u = 0; u < ml; ++u) {
-        int tu[N], ui[N];
-        CT2 w[N];
-#pragma unroll
-        for (int j = 0; j < N; ++j) tu[j] = blist[lo[j] + (u < len[j] ? u : 0)];
-#pragma unroll
-        for (int j = 0; j < N; ++j) { w[j] = ld(tu[j]); ui[j] = S.citems[tu[j]]; }
-#pragma unroll
-        for (int j = 0; j < N; ++j)
-          rk[j] += u < len[j] && ((w[j].x < v[j].x) ||
-                                  (w[j].x == v[j].x &&
-                                   (w[j].y < v[j].y || (w[j].y == v[j].y && ui[j] < vi[j]))));
+      for (int u = 0; u < len; ++u) {
+        const int tu = blist[lo + u];
+        const CT2 w = ld(tu);
+        const int ui = S.citems[tu];
+        rk += (w.x < v.x) || (w.x == v.x && (w.y < v.y || (w.y == v.y && ui < vi)));
       }
-      it.each(first, V, [&](int j, int) { S.vrank[t[j]] = (uint16_t)rk[j]; });
-    });
+      S.vrank[t] = (uint16_t)rk;
+    }
     if (tid == 0) H.base = (int64_t)resv;   // (the reservation's round trip ends here)
     __syncthreads();
     // every thread reads the base; an output overflow skips P6 (the host regrows and re-runs)
@@ -2290,18 +2109,12 @@ void k_fused(FusedArgs A) {
     // scores of the clique vertices into LDS by row rank when they fit in parent..scell
     c.S.vstaged = 8 * H.V <= L.off_citems - L.off_parent;
     if (c.S.vstaged) {
-      in_flight<NF_P6A, FWG>(tid, n, [&](auto it, int first) {
-        constexpr int N = decltype(it)::n;
-        int f[N], vr[N], li[N];
-        double sc[N];
-        it.each(first, n, [&](int j, int t) {
-          f[j] = S.flags[t];
-          vr[j] = S.vrank[t];
-          li[j] = S.citems[t];
-        });
-        it.each(first, n, [&](int j, int) { if (f[j] == 3) sc[j] = c.score[b0 + li[j]]; });
-        it.each(first, n, [&](int j, int) { if (f[j] == 3) c.S.vscore[vr[j]] = sc[j]; });
-      });
+      // (flag, rank and file index loaded together, before the flag is tested)
+      for (int t = tid; t < n; t += FWG) {
+        const int f = S.flags[t], vr = S.vrank[t], li = S.citems[t];
+        if (f != 3) continue;
+        c.S.vscore[vr] = c.score[b0 + li];
+      }
       __syncthreads();
     }
 

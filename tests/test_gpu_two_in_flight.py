@@ -1,12 +1,12 @@
 """The staged per-box, per-edge and per-vertex loops of the fused kernel's P1, P2c, P3, P5 and
-P6a (rgc_fused.hip: Items / in_flight).
+P6a (rgc_fused.hip).
 
-Each loop's body is written in stages over the items of a thread (i, i + FWG; P1: the RB
-register boxes), every stage loading what it needs before the next uses it.  The product runs
-the bodies one item at a time (fused_two selects no phase for the pair form; RGC_TWO_MASK
-builds select some), so a thread's second item, and any item behind it, goes through the same
-body again.  The cases are the smallest micrographs at which that can go wrong, in either
-form: total box counts around the places where a thread gains or loses its second item in each
+Each loop is a plain `for (i = tid; i < n; i += FWG)` loop (P1: the RB register boxes, then
+the HBM tail) whose iteration is staged: the loads at known addresses first, then the flag
+test, then the action.  A thread's second item, and any item behind it, goes through the same
+body again.  (The module's name dates from the form that ran two items of a thread at once,
+measured and not selected.)  The cases are the smallest micrographs at which that can go
+wrong: total box counts around the places where a thread gains or loses its second item in each
 instance (256 threads: RB = 4, classes up to 512 boxes; 512 threads: RB = 2; 768 threads:
 classes 1409..1536), a thread's items in one packed counter word (P1's cell counters, P5's
 x-bucket counters), its edges in one component, the per-box union of the capacity regime
