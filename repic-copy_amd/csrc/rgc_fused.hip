@@ -59,6 +59,12 @@ constexpr int MAXW = 16;            // reduction slots: up to 1024-thread workgr
 // 1024: C3's ~4.1k boxes all stay in registers, VGPRs to spare at 4 waves per SIMD; boxes past
 // RB * NT are re-read from HBM in each of P0's and P1's passes)
 constexpr int fused_rb(int nt) { return nt <= 256 ? 4 : nt >= 1024 ? 5 : 2; }
+// of those, the boxes whose P1 key and arrival ordinal stay in a register from the count to
+// the placement (the others park both in LDS), and the positions whose P5 bucket and ordinal
+// stay in one across the scan.  The 1024-thread instances hold none: with five more live
+// registers in P1 or P5 they drop an occupancy step (`make resources`).
+constexpr int fused_rq(int nt) { return nt >= 1024 ? 0 : fused_rb(nt); }
+constexpr int fused_rv(int nt) { return nt >= 1024 ? 0 : fused_rb(nt); }
 // The per-box / per-edge / per-vertex loops of P1, P2c, P3, P5 and P6a run one item of a thread
 // at a time, each iteration staged: its loads at known addresses first, then the flag test,
 // then the action.  That order is the measured gain.  Keeping two items of a thread in flight
@@ -67,7 +73,8 @@ constexpr int fused_rb(int nt) { return nt <= 256 ? 4 : nt >= 1024 ? 5 : 2; }
 // Two barriers are off the workgroup's chain because their work sits in front of one that is
 // there anyway: P5's counter zeroing in front of P4's reservation barrier, and P3b's stats
 // summed behind P4's barriers when --get_cc is off (profiles/r12; the switches that timed
-// them rebuild from 25f33ec).
+// them rebuild from 25f33ec).  A third goes with P3b's second loop: the compress loop takes the
+// stats itself, and where P4's root pass only reads (the one-trip form) nothing waits for it.
 
 struct FusedHdr {
   // reduction scratch: the single-value reductions alias the 4-way one (every reduction
@@ -147,7 +154,9 @@ struct FShared {
   uint16_t* vrank;
   uint8_t* flags;   // by local index: 0 no edge, 1 graph node, 3 clique vertex
   uint16_t* dst;
-  uint16_t* split;  // P3-P4 (scell region): end of each box's first picker segment in dst
+  uint16_t* split;  // P2-P4 (scell region): end of each box's first picker segment in dst,
+                    // written by P2 beside fwd (position ts's slot once its thread has read
+                    // scell[ts])
   uint16_t* cbuf;   // P4-P6 (cell starts): clique queue, or the current chunk of the re-walk
   double* vscore;   // P6 (parent..scell, dead after P5): score of each clique vertex by row
                     // rank, used when 8 V bytes fit there (vstaged); else scores are
@@ -1102,14 +1111,19 @@ __device__ __forceinline__ void stencil_spans3(const Stencil& st, const FShared&
 // the candidate's position t and its ordinal kk.  One flattened loop per target grid (not
 // unrolled: a grid's stencil holds a few candidates).  K = 3 leaves its two spans in g0, g1
 // for the list write that follows the count.
-template <int K, typename F>
+// first_done() runs once, behind the first target grid (picker st.p + 1), when the box has one:
+// the grids are walked in ascending picker order, so the edges counted up to there are the
+// first picker segment of the box's list (P4's split).
+template <int K, typename F, typename G1>
 __device__ __forceinline__ void stencil_walk(const Stencil& st, const FShared& S,
-                                             const GridU& H, Span& g0, Span& g1, F&& body) {
+                                             const GridU& H, Span& g0, Span& g1, F&& body,
+                                             G1&& first_done) {
   int kk = 0;
   if constexpr (K == 3) {
     stencil_spans3(st, S, H, g0, g1);
 #pragma unroll 1
     for (int j = 0; j < g0.n; ++j, ++kk) body(g0.at(j), kk);
+    first_done();
 #pragma unroll 1
     for (int j = 0; j < g1.n; ++j, ++kk) body(g1.at(j), kk);
   } else {
@@ -1119,6 +1133,7 @@ __device__ __forceinline__ void stencil_walk(const Stencil& st, const FShared& S
       const Span g = span_of(b);
 #pragma unroll 1
       for (int j = 0; j < g.n; ++j, ++kk) body(g.at(j), kk);
+      if (q == st.p + 1) first_done();
     }
   }
 }
@@ -1176,12 +1191,15 @@ struct EdgeP {
 // candidate of a higher picker; returns the edge count and, for the list write, either the
 // targets themselves (at most 2 edges: first << 16 | second, ascending) or the bitmask of edge
 // candidates (candidates 0..31 in stencil order; later candidates are re-tested by the write).
+// *first_out: the edges into the next picker's grid (every one counted, past candidate 31
+// too), i.e. the length of the list's first picker segment.
 template <int K, bool W>
 __device__ __forceinline__ int pairs_count(const Stencil& st, const FShared& S, const GridU& H,
                                            double B, double two_b2, double i_lo, double i_hi,
-                                           Span& g0, Span& g1, uint32_t* mask_out) {
+                                           Span& g0, Span& g1, uint32_t* mask_out,
+                                           int* first_out) {
   uint32_t mask = 0, pk = 0;
-  int cnt = 0;
+  int cnt = 0, first = 0;
   // f32 layout: reject in f32 first.  An edge needs both overlaps > (6/13) B, i.e. |dx| and
   // |dy| < (7/13) B = 0.5385 B; the f32 difference of two exact f32 values is within 2^-24 of
   // the true one, so |dx| >= 0.54 B (as computed) can never be an edge.
@@ -1202,8 +1220,9 @@ __device__ __forceinline__ int pairs_count(const Stencil& st, const FShared& S, 
       mask |= (kk < 32) ? (1u << kk) : 0u;
       pk = (pk << 16) | (uint32_t)t;
     }
-  });
+  }, [&]() { first = cnt; });
   *mask_out = cnt <= FILL_FAST ? pk : mask;
+  *first_out = first;
   return cnt;
 }
 
@@ -1211,9 +1230,9 @@ __device__ __forceinline__ int pairs_count(const Stencil& st, const FShared& S, 
 template <int K>
 __device__ __forceinline__ int pairs_count_int(const Stencil& st, const FShared& S,
                                                const GridU& H, float Bf, float Tf, Span& g0,
-                                               Span& g1, uint32_t* mask_out) {
+                                               Span& g1, uint32_t* mask_out, int* first_out) {
   uint32_t mask = 0, pk = 0;
-  int cnt = 0;
+  int cnt = 0, first = 0;
   const float ax = (float)st.a.x, ay = (float)st.a.y;
   stencil_walk<K>(st, S, H, g0, g1, [&](int t, int kk) {
     const float2 bf = reinterpret_cast<const float2*>(S.sxy)[t];
@@ -1224,8 +1243,9 @@ __device__ __forceinline__ int pairs_count_int(const Stencil& st, const FShared&
       mask |= (kk < 32) ? (1u << kk) : 0u;
       pk = (pk << 16) | (uint32_t)t;
     }
-  });
+  }, [&]() { first = cnt; });
   *mask_out = cnt <= FILL_FAST ? pk : mask;
+  *first_out = first;
   return cnt;
 }
 
@@ -1431,6 +1451,7 @@ void k_fused(FusedArgs A) {
   // ---- P0: load coordinates (the first RB boxes of each thread stay in registers for P1),
   // bounding box (one combined workgroup reduction)
   constexpr int RB = fused_rb(NT);
+  constexpr int RQ = fused_rq(NT), RV = fused_rv(NT);
   double rx[RB], ry[RB];
 #pragma unroll
   for (int j = 0; j < RB; ++j) {
@@ -1569,53 +1590,83 @@ void k_fused(FusedArgs A) {
   const GridU G = grid_u(H);
   const int nk = G.nkey;
   // counting sort by key with packed u16 counters (two keys per LDS word, zeroed in P0).
-  // Counts go to slot key + 1, so the exclusive scan leaves bucket q's start in slot q + 1;
-  // the scatter's cursors advance it to bucket q's end = bucket q+1's start, which leaves
-  // cstart[q] = start of bucket q for q = 0..nk+1 with no rebuild pass.  The key waits in
-  // pos[i] between the passes.
+  // The count's atomic returns: its old value is the box's arrival ordinal within its bucket.
+  // Counts go to slot key, so the exclusive scan leaves cstart[q] = start of bucket q for
+  // q = 0..nk and the total n in cstart[nk + 1], and nothing advances them afterwards.  Key and
+  // ordinal of a register box (the first RB of a thread) stay in one register, key | ordinal
+  // << 16 (both < 2^16), from the count to the placement; a box behind them (more than RB * NT
+  // boxes) parks its key in pos[i] and its ordinal in citems[i], free until the placement.
   uint32_t* cw = reinterpret_cast<uint32_t*>(S.cstart);
-  each_box([&](int i, double xv, double yv) {
-    const int q = box_key<W>(G, picker_of<K>(c.pb, i), xv, yv) + 1;
-    S.pos[i] = (uint16_t)q;
-    atomicAdd(&cw[q >> 1], 1u << (16 * (q & 1)));
-  });
-  __syncthreads();
-  block_scan_dpp32<FWG>(S.cstart, nk + 2, H.redi);
-  // arrival order into fwd (free until P2), made deterministic by the placement pass
-  uint16_t* arrival = S.fwd;
-  each_box([&](int i, double, double) {
-    const int q = S.pos[i];
+  auto count_box = [&](int i, double xv, double yv) {
+    const int q = box_key<W>(G, picker_of<K>(c.pb, i), xv, yv);
     const uint32_t t = atomicAdd(&cw[q >> 1], 1u << (16 * (q & 1)));
-    arrival[(t >> (16 * (q & 1))) & 0xFFFF] = (uint16_t)i;
-  });
+    return (uint32_t)q | (((t >> (16 * (q & 1))) & 0xFFFFu) << 16);
+  };
+  auto park = [&](int i, uint32_t v) {
+    S.pos[i] = (uint16_t)(v & 0xFFFFu);
+    S.citems[i] = (uint16_t)(v >> 16);
+  };
+  uint32_t rq[RQ > 0 ? RQ : 1];
+#pragma unroll
+  for (int j = 0; j < RB; ++j) {
+    const int i = tid + j * FWG;
+    if (j < RQ) rq[j] = 0;
+    if (i < n) {
+      const uint32_t v = count_box(i, rx[j], ry[j]);
+      if (j < RQ) rq[j] = v;
+      else park(i, v);
+    }
+  }
+  for (int i = tid + RB * FWG; i < n; i += FWG) park(i, count_box(i, ax[b0 + i], ay[b0 + i]));
+  __syncthreads();
+  block_scan_dpp32<FWG>(S.cstart, nk + 1, H.redi);
+  // arrival order into fwd (free until P2): bucket start + ordinal, one load and no atomic;
+  // made deterministic by the placement pass
+  uint16_t* arrival = S.fwd;
+#pragma unroll
+  for (int j = 0; j < RQ; ++j) {
+    const int i = tid + j * FWG;
+    if (i < n) arrival[S.cstart[rq[j] & 0xFFFFu] + (rq[j] >> 16)] = (uint16_t)i;
+  }
+  for (int i = tid + RQ * FWG; i < n; i += FWG) {
+    const int q = S.pos[i], o = S.citems[i];
+    arrival[S.cstart[q] + o] = (uint16_t)i;
+  }
   __syncthreads();
   // placement: by local index inside each bucket (buckets hold a few boxes).  Written per
   // box, not through each_box: each stage tests i < n on its own and the walk stands outside
   // those tests (a thread without the box walks an empty bucket).  With the whole body under
   // one test the compiler fuses the two bounds into one 32-bit LDS read at a 2-byte-aligned
   // address and the 1024-thread K = 4 instance needs another register.
-  auto place = [&](int i, auto&& xy) {
+  // (key(): the register box's key from its register, a later box's from pos[i])
+  auto place = [&](int i, auto&& key, auto&& xy) {
     int q = 0, lo = 0, len = 0;
-    if (i < n) q = S.pos[i];
+    if (i < n) q = key();
     if (i < n) {
-      lo = S.cstart[q - 1];
-      len = (int)S.cstart[q] - lo;
+      lo = S.cstart[q];
+      len = (int)S.cstart[q + 1] - lo;
     }
     int t = lo;
 #pragma nounroll
     for (int u = 0; u < len; ++u) t += (int)arrival[lo + u] < i ? 1 : 0;
     if (i < n) {
       const double2 v = xy();
-      S.scell[t] = (uint16_t)(q - 1);
+      S.scell[t] = (uint16_t)q;
       S.citems[t] = (uint16_t)i;
       S.pos[i] = (uint16_t)t;
       st_xy<W>(S, t, v.x, v.y);
     }
   };
 #pragma unroll
-  for (int j = 0; j < RB; ++j) place(tid + j * FWG, [&]() { return make_double2(rx[j], ry[j]); });
+  for (int j = 0; j < RB; ++j) {
+    const int i = tid + j * FWG;
+    if (j < RQ) place(i, [&]() { return (int)(rq[j < RQ ? j : 0] & 0xFFFFu); },
+                      [&]() { return make_double2(rx[j], ry[j]); });
+    else place(i, [&]() { return (int)S.pos[i]; }, [&]() { return make_double2(rx[j], ry[j]); });
+  }
   for (int i = tid + RB * FWG; i < n; i += FWG)
-    place(i, [&]() { return make_double2(ax[b0 + i], ay[b0 + i]); });
+    place(i, [&]() { return (int)S.pos[i]; },
+          [&]() { return make_double2(ax[b0 + i], ay[b0 + i]); });
   __syncthreads();
   // picker bounds in position space: grid p occupies [pp[p], pp[p+1]); non-finite boxes follow
 #pragma unroll
@@ -1663,17 +1714,23 @@ void k_fused(FusedArgs A) {
       Stencil st;
       Span g0, g1;
       uint32_t mask = 0;
-      int ec = 0;
+      int ec = 0, ec1 = 0;   // edges; those to the next picker (the first target grid)
       if (act) {
         stencil_setup<K, W>(st, ts, S, G);
-        if constexpr (!W) ec = pairs_count_int<K>(st, S, G, (float)B, (float)ti, g0, g1, &mask);
-        else ec = pairs_count<K, W>(st, S, G, B, two_b2, i_lo, i_hi, g0, g1, &mask);
+        if constexpr (!W)
+          ec = pairs_count_int<K>(st, S, G, (float)B, (float)ti, g0, g1, &mask, &ec1);
+        else ec = pairs_count<K, W>(st, S, G, B, two_b2, i_lo, i_hi, g0, g1, &mask, &ec1);
       }
       const bool top = (ts & 63) == 63;   // the lane that writes the block's end
       // (lanes past the last box store too: fwd[n] is the end of box n - 1's list unless that
       // box closes its block; the slots lie within the fwd_blocks(nmax) * 64 begins)
+      // split[ts], the end of the first picker segment of the box's list, is written beside
+      // fwd[ts] for every box: begin + ec1 (an empty list or segment: the begin).  split
+      // aliases scell, and scell[ts] is read exactly once, by this thread in stencil_setup
+      // above, so no other thread can still need the slot.  (Boxes only: scell has n slots.)
       if (__ballot(ec != 0) == 0) {   // (no edge in the block, e.g. the last picker's)
         S.fwd[ts] = 0;
+        if (act) S.split[ts] = 0;
         if (top) S.bend[ts >> 6] = 0;
         continue;
       }
@@ -1685,6 +1742,7 @@ void k_fused(FusedArgs A) {
       const int base = ufl((int)rb);
       const int off = base + (odd ? total - incl : incl - ec);
       S.fwd[ts] = (uint16_t)off;
+      if (act) S.split[ts] = (uint16_t)(off + ec1);
       if (top) S.bend[ts >> 6] = (uint16_t)(base + total);
       if (base + total > A.ecap || ec == 0) continue;
       uint16_t* d = S.dst + off;
@@ -1813,44 +1871,45 @@ void k_fused(FusedArgs A) {
   
   // ---- P3: connected components: the unions ran in the P2 fill; compress, count sizes
   STAMP(6);   // union (one thread per edge)
-  // the flag, the list bounds and the parent are loaded together, before the flag is tested: a
-  // box that is no node searches an empty range
-  for (int i = tid; i < n; i += FWG) {
-    const int f = S.flags[i];
-    const int lo = S.eb(i), hi = S.ee(i);
-    uint32_t p = 0;
-    if (cc32) p = lds_ld(S.cnt + i);
-    const int sp = lb16s(S.dst, lo, f ? hi : lo, next_picker_end<K>(c.pp, i));
-    if (!f) continue;
-    S.split[i] = (uint16_t)sp;   // every node
-    const uint32_t r = cc32 ? uf_find32p(S.cnt, i, p) : uf_find_lds(S.parent, i);
-    p16_st(S.parent + i, r);
-    atomicAdd(&ccsz[r >> 1], 1u << (16 * (r & 1)));
-  }
-  __syncthreads();
-  auto cc_size = [&](uint32_t r) { return (int)((ccsz[r >> 1] >> (16 * (r & 1))) & 0xFFFF); };
+  // One loop compresses and takes the stats.  The flag and the parent are loaded together,
+  // before the flag is tested (the list split P4 reads came from P2's count).  The size
+  // counter's atomic returns: sizes only grow, so the last increment of the largest component
+  // returns its final size minus one, and the largest size is the maximum of old + 1 over all
+  // increments.  Nodes: the flag is set; roots: the find returned the box itself.
   const bool get_cc = (A.flags & 1) != 0;
   int nodes = 0, cc_max = 0;
   // per-wave partials in redd: no scan of P4 uses it (the one-trip scans red64, the general
   // form redi), so they survive until they are read
   int* const sred = reinterpret_cast<int*>(H.redd);
   {
-    // nodes and roots packed in one 64-bit sum, the largest size in one max; every thread
-    // reads the per-wave partials (no thread-0 section and second barrier)
-    // nodes << 16 | roots (both <= n < 2^16) in one 32-bit sum
+    // nodes << 16 | roots (both <= n < 2^16) in one 32-bit sum, the largest size in one max;
+    // every thread reads the per-wave partials (no thread-0 section and second barrier)
     int nr = 0;
     int mx = 0;
     for (int i = tid; i < n; i += FWG) {
-      const int f = S.flags[i], p = S.parent[i];
-      const uint32_t sz = ccsz[i >> 1];
+      const int f = S.flags[i];
+      uint32_t p = 0;
+      if (cc32) p = lds_ld(S.cnt + i);
       if (!f) continue;
-      nr += 1 << 16;
-      if (p == i) { nr += 1; mx = max(mx, (int)((sz >> (16 * (i & 1))) & 0xFFFF)); }
+      const uint32_t r = cc32 ? uf_find32p(S.cnt, i, p) : uf_find_lds(S.parent, i);
+      p16_st(S.parent + i, r);
+      const uint32_t old = atomicAdd(&ccsz[r >> 1], 1u << (16 * (r & 1)));
+      nr += (1 << 16) + (r == (uint32_t)i ? 1 : 0);
+      mx = max(mx, (int)((old >> (16 * (r & 1))) & 0xFFFFu) + 1);
     }
     nr = wave_incl_add32(nr);
     mx = wave_incl_max32(mx);
     if ((tid & 63) == 63) { sred[tid >> 6] = nr; sred[MAXW + (tid >> 6)] = mx; }
   }
+  // The finds above walk and compress parent chains through other boxes' entries (cnt, or the
+  // u16 parents), so nothing may overwrite an entry while some thread is still in the loop.
+  // P4's one-trip root pass writes nothing in front of its scan barrier: it reads fwd / bend,
+  // dst and its root's split, all final since P2 (and, with --get_cc, parent behind the
+  // barrier below), and the chunk table is first written behind a BFS.  The general root pass
+  // and the DFS fallback store per-root counts into cnt, the u32 parents, in front of their
+  // first barrier: instances and micrographs that take them keep the barrier here.
+  if (!(bfs_one_trip(K, NT) && c.pp[1] <= NT)) __syncthreads();
+  auto cc_size = [&](uint32_t r) { return (int)((ccsz[r >> 1] >> (16 * (r & 1))) & 0xFFFF); };
   // the per-wave partials of the stats, once a barrier is behind them
   auto cc_stats = [&]() {
     int t = 0;
@@ -1947,7 +2006,8 @@ void k_fused(FusedArgs A) {
   {
     int r0 = 0, len = n0;
     bool ok = maxch >= 1;
-    if (tid == 0) { chtab[0] = 0; chtab[1] = 0; }
+    // (chtab[0..1], the table's origin, is written with the first chunk, behind that BFS's
+    // barriers: the table lies in cnt, where P3b's finds may still be walking parents)
     while (ok && r0 < n0) {
       len = min(len, n0 - r0);
       if (QG && K <= 4 && qslot >= 0)
@@ -1967,7 +2027,11 @@ void k_fused(FusedArgs A) {
       C += bo.C;
       r0 += len;
       ++nch;
-      if (tid == 0) { chtab[2 * nch] = (uint32_t)r0; chtab[2 * nch + 1] = (uint32_t)C; }
+      if (tid == 0) {
+        if (nch == 1) { chtab[0] = 0; chtab[1] = 0; }
+        chtab[2 * nch] = (uint32_t)r0;
+        chtab[2 * nch + 1] = (uint32_t)C;
+      }
       // next chunk: as many roots as the tightest level of this one leaves room for
       len = max(len + 1, (int)((float)len * fminf(bo.fit, 2.0f) * 0.95f));
     }
@@ -2052,20 +2116,43 @@ void k_fused(FusedArgs A) {
     auto ld = [&](int t) -> CT2 { return reinterpret_cast<const CT2*>(S.sxy)[t]; };
     const CT minx = (CT)H.minx, xbs = (CT)H.xbs, nlast = (CT)(n - 1);
     auto xbucket = [&](CT xv) { return (int)fmin((xv - minx) * xbs, nlast); };
-    // count: the vertex's ordinal within its bucket waits in vrank (flag and x loaded together,
-    // before the flag is tested)
-    for (int t = tid; t < n; t += FWG) {
-      const int f = S.flags[t];
-      const CT x = ld(t).x;
-      if (f != 3) continue;
+    // count (flag and x loaded together, before the flag is tested): the atomic returns the
+    // vertex's ordinal within its bucket.  Bucket and ordinal of a thread's first RV positions
+    // stay in one register across the scan, bucket | ordinal << 16 (NOV: no vertex; a bucket
+    // is < n <= 65535, so no vertex packs to it), and the scatter is one load and one store; a
+    // position behind them parks its ordinal in vrank and recomputes its bucket.
+    constexpr uint32_t NOV = ~0u;
+    auto count_vertex = [&](int f, CT x) {
+      if (f != 3) return NOV;
       const int q = xbucket(x);
       const uint32_t r = atomicAdd(&bw[q >> 1], 1u << (16 * (q & 1)));
-      S.vrank[t] = (uint16_t)((r >> (16 * (q & 1))) & 0xFFFFu);
+      return (uint32_t)q | (((r >> (16 * (q & 1))) & 0xFFFFu) << 16);
+    };
+    uint32_t rv[RV > 0 ? RV : 1];
+#pragma unroll
+    for (int j = 0; j < RV; ++j) {
+      const int t = tid + j * FWG;
+      int f = 0;
+      CT x = 0;
+      if (t < n) {
+        f = S.flags[t];
+        x = ld(t).x;
+      }
+      rv[j] = count_vertex(f, x);
+    }
+    for (int t = tid + RV * FWG; t < n; t += FWG) {
+      const int f = S.flags[t];
+      const CT x = ld(t).x;
+      const uint32_t v = count_vertex(f, x);
+      if (v != NOV) S.vrank[t] = (uint16_t)(v >> 16);
     }
     __syncthreads();
     const int V = block_scan_dpp32<FWG>(bcnt, n, H.redi);
     if (tid == 0) { H.V = (int)V; bcnt[n] = (uint16_t)V; }
-    for (int t = tid; t < n; t += FWG) {
+#pragma unroll
+    for (int j = 0; j < RV; ++j)
+      if (rv[j] != NOV) blist[bcnt[rv[j] & 0xFFFFu] + (rv[j] >> 16)] = (uint16_t)(tid + j * FWG);
+    for (int t = tid + RV * FWG; t < n; t += FWG) {
       const int f = S.flags[t];
       const CT x = ld(t).x;
       const int vr = S.vrank[t];
