@@ -60,11 +60,15 @@ def mg_status(ex, gap=0.0, primal=0.0):
     return GAP_OK
 
 
-def solve_batch(ctx, mats, weights, node_limit=0, timing=False, statuses=False, gaps=False):
+def solve_batch(ctx, mats, weights, node_limit=0, timing=False, statuses=False, gaps=False,
+                columns=False):
     """Returns (x list of uint8 arrays, exact list of bool): per micrograph the chosen
     columns and whether every component was proven optimal (with ``statuses``: the
     micrograph status codes, mg_status, instead of the bools; with ``gaps`` also the
-    micrograph's relative gap bound, sum of component gaps / objective).  The search is
+    micrograph's relative gap bound, sum of component gaps / objective; with ``columns`` the
+    tuple ends with a list of (exact, gap) per micrograph: rgc_ilp_solve's raw per-column
+    arrays, the status of each column's component and the component's absolute gap at one of
+    its columns).  The search is
     bounded by ``node_limit`` nodes per component (0: the library default) and nothing else,
     so the result is the same on every run and device."""
     col_ptr, row_idx, n_rows, col_off = pack(mats)
@@ -90,6 +94,8 @@ def solve_batch(ctx, mats, weights, node_limit=0, timing=False, statuses=False, 
         g = float(gp[a:b].sum())
         st.append(mg_status(ex[a:b], g, primal))
         rel.append(g / primal if primal > 0 else (0.0 if g == 0 else float("inf")))
-    if statuses:
-        return (xs, st, rel) if gaps else (xs, st)
-    return xs, [s_ == OPTIMAL for s_ in st]
+    out = ((xs, st, rel) if gaps else (xs, st)) if statuses else (xs, [s_ == OPTIMAL for s_ in st])
+    if columns:
+        out += ([(ex[col_off[m]:col_off[m + 1]], gp[col_off[m]:col_off[m + 1]])
+                 for m in range(len(mats))],)
+    return out

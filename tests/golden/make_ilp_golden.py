@@ -6,7 +6,9 @@ gap 0) on the same models.  The large ones (C3 micrographs, C5 windows with comp
 computed once here and committed: ``ilp_highs.npz`` maps a sha256 of each model (shape, COO
 rows/cols, f32 weights) to the HiGHS objective and its packing (chosen column indices).
 ``tests/test_ilp.py:highs`` fails for a model that is not in the file (no live solves on the
-GPU box).
+GPU box).  The edge models of tests/ilp_models.py above 200 columns are registered here too.
+A run merges: entries already in the file are kept as they are, only missing models are solved
+and appended.
 
     python tests/golden/make_ilp_golden.py
 """
@@ -52,13 +54,22 @@ def main():
     sys.path[:0] = [os.path.join(ROOT, "tests"), ROOT, os.path.join(ROOT, "repic-copy_amd")]
     import time
 
+    import ilp_models
     import test_ilp
     from oracle import ilp_ref
     probs = (test_ilp.golden_problems() + test_ilp.golden_problems("syn_k4") +
              test_ilp.golden_problems("syn_k5") + test_ilp.synthetic_problems("C2", 60) +
              test_ilp.synthetic_problems("C4", 20) + test_ilp.synthetic_problems("C3", 3) +
-             test_ilp._c5_window_problems(640, 2))
+             test_ilp._c5_window_problems(640, 2) +
+             [ilp_models.model(n) for n in ilp_models.fixture_models()])
+    # merge: the entries already in the file stay as they are (same order, same values); only
+    # the models missing from it are solved and appended
     keys, obj, idx, off = [], [], [], [0]
+    if os.path.exists(OUT):
+        with np.load(OUT, allow_pickle=False) as z:
+            keys, obj = z["keys"].tolist(), z["obj"].tolist()
+            idx, off = [z["idx"]], z["off"].tolist()
+    n_old = len(keys)
     t0 = time.time()
     for A, w in probs:
         k = model_key(A, w)
@@ -71,8 +82,8 @@ def main():
         idx.append(sel)
         off.append(off[-1] + len(sel))
     np.savez_compressed(OUT, keys=np.array(keys), obj=np.array(obj, np.float64),
-                        off=np.array(off, np.int64), idx=np.concatenate(idx))
-    print(f"{len(keys)} models, {time.time() - t0:.1f} s -> {OUT}")
+                        off=np.array(off, np.int64), idx=np.concatenate(idx).astype(np.int32))
+    print(f"{len(keys)} models ({len(keys) - n_old} new), {time.time() - t0:.1f} s -> {OUT}")
 
 
 if __name__ == "__main__":
