@@ -586,7 +586,13 @@ __global__ __launch_bounds__(WG) void k4_compress(int N, const uint8_t* __restri
                                                   int32_t* parent, int32_t* csize) {
   const int g = blockIdx.x * WG + threadIdx.x;
   if (g >= N || !has_edge[g]) return;
-  const int r = uf_find(parent, g);
+  // (a walk without uf_find's path-halving stores: this kernel writes roots into the array
+  // other threads still walk, and a halving store of a walk that read parent[g] before its
+  // root went in could land after it and leave a non-root there.  Seen after k4_union at
+  // 39937 boxes: --get_cc lost roots of the target component.  After k4_union_lds every
+  // parent is a root already, and neither walk stores.)
+  int r = g;
+  for (int p; (p = ld_par(parent, r)) != r;) r = p;
   __hip_atomic_store(parent + g, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   // the lanes in the first active lane's component add once (a dense micrograph's giant
   // component would otherwise queue one atomic per box on one address)

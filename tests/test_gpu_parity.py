@@ -71,14 +71,14 @@ def test_gpu_process_writer_matches_reference_golden(name, tmp_path, monkeypatch
 
 
 # ----------------------------------------------------------------------------- vs oracle
-def _oracle_mg(mg, box, methods, id_base, get_cc=False):
+def _oracle_mg(mg, box, methods, id_base, get_cc=False, multi_out=False):
     from oracle import cpu_ref
     coords, nid = [], id_base
     for (x, y, s) in mg:
         coords.append([(float(a), float(b), float(c), nid + i)
                        for i, (a, b, c) in enumerate(zip(x, y, s))])
         nid += len(x)
-    return cpu_ref.micrograph(coords, box, methods, get_cc=get_cc)
+    return cpu_ref.micrograph(coords, box, methods, get_cc=get_cc, multi_out=multi_out)
 
 
 def _canon(rows, w, conf, cons_xyid):
@@ -87,15 +87,17 @@ def _canon(rows, w, conf, cons_xyid):
             np.asarray(conf)[perm].view(np.uint32), [cons_xyid[i] for i in perm])
 
 
-def _check_vs_oracle(mgs, k, box, get_cc=False, no_fused=False):
+def _check_vs_oracle(mgs, k, box, get_cc=False, no_fused=False, multi_out=False):
+    """multi_out: the members of each clique in the --multi_out order (the device's ``order``
+    applied to its members) against the oracle's --multi_out rows, instead of the consensus."""
     from repic_amd import _lib
     from repic_amd.pipeline import Batch, run_batch
     batch = Batch.pack(k, box, mgs)
     ctx = _lib.Context(0)
-    res = run_batch(ctx, batch, get_cc=get_cc, no_fused=no_fused)
+    res = run_batch(ctx, batch, get_cc=get_cc, no_fused=no_fused, multi_out=multi_out)
     methods = [f"picker{p}" for p in range(k)]
     for m, mg in enumerate(mgs):
-        o = _oracle_mg(mg, box, methods, int(batch.id_base[m]), get_cc)
+        o = _oracle_mg(mg, box, methods, int(batch.id_base[m]), get_cc, multi_out)
         r = res[m]
         assert r.status == _lib.OK
         assert (r.cc_max, r.cc_cnt) == (o["cc_max"], o["cc_cnt"])
@@ -105,8 +107,16 @@ def _check_vs_oracle(mgs, k, box, get_cc=False, no_fused=False):
         assert r.n_vert == A.shape[0] and len(r.w) == C
         b0 = int(batch.box_off[m * k])
         idb = int(batch.id_base[m]) - b0
-        gcons = [(float(batch.x[g]), float(batch.y[g]), idb + int(g)) for g in r.consensus]
-        a = _canon(orows, o["w"], o["conf"], o["consensus"])
+        def tup(g):
+            return (float(batch.x[g]), float(batch.y[g]), idb + int(g))
+        gcons, ocons = [tup(g) for g in r.consensus], o["consensus"]
+        if multi_out:
+            # the oracle's table: the header, a row per clique (members of pickers 0..k-2 in
+            # node-iteration order, then picker k-1's), then the boxes outside every clique
+            ocons = [list(row) for row in ocons[1:1 + C]]
+            gcons = [[tup(mem[p]) for p in od if p != k - 1] + [tup(mem[k - 1])]
+                     for mem, od in zip(r.members.tolist(), r.order.tolist())]
+        a = _canon(orows, o["w"], o["conf"], ocons)
         b = _canon(r.rows, r.w, r.conf, gcons)
         assert np.array_equal(a[0], b[0])
         assert np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
@@ -217,10 +227,11 @@ def test_gpu_full_c2_properties():
     ctx.close()
 
 
-def _check_vs_vec(mgs, k, box, get_cc=False, no_fused=False, ctx=None):
+def _check_vs_vec(mgs, k, box, get_cc=False, no_fused=False, ctx=None, allow_empty=False):
     """Every output of the HIP path against the vectorised oracle (oracle/cpu_vec.py, pinned
     to oracle/cpu_ref.py), bit-exact, at full BASELINE sizes: clique member sets, COO rows,
-    float32 w / conf, consensus box, CC stats."""
+    float32 w / conf, consensus box, CC stats.  allow_empty: a micrograph without edges or
+    without cliques is held to the oracle's status, CC stats and edge count."""
     from oracle import cpu_vec
     from repic_amd import _lib
     from repic_amd.pipeline import Batch, run_batch
@@ -240,6 +251,13 @@ def _check_vs_vec(mgs, k, box, get_cc=False, no_fused=False, ctx=None):
         o = cpu_vec.micrograph(x, y, s, [len(t[0]) for t in mg], box, get_cc=get_cc,
                                id_base=int(batch.id_base[m]))
         r = res[m]
+        if allow_empty and o["status"] != "ok":
+            code = {"no_edges": _lib.NO_EDGES, "no_cliques": _lib.NO_CLIQUES}[o["status"]]
+            for q in (r, res_nm[m]):
+                assert q.status == code and len(q.w) == 0 and q.n_edges == o["n_edges"]
+                if "cc_max" in o:
+                    assert (q.cc_max, q.cc_cnt) == (o["cc_max"], o["cc_cnt"])
+            continue
         assert o["status"] == "ok" and r.status == _lib.OK
         assert (r.cc_max, r.cc_cnt) == (o["cc_max"], o["cc_cnt"])
         assert r.n_edges == o["n_edges"] and r.n_vert == o["V"]
