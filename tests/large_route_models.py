@@ -1,5 +1,5 @@
 """Inputs that sit on the routing and size edges of the large-micrograph route (rgc_kernels.hip,
-rgc_cliques.hip, run_multi in rgc_abi.cpp), shared by tests/test_large_route_models.py (which
+rgc_cliques.hip, run_multi in rgc_run_large.cpp), shared by tests/test_large_route_models.py (which
 pins every input on its edge with the oracle alone) and tests/test_gpu_large_route_edges.py.
 
 The route a micrograph takes is not reported by the ABI; it is a pure function of the box

@@ -1,4 +1,4 @@
-"""The set-packing solver (rgc_ilp.hip, ilp_core / ilp_solve_rec of rgc_abi.cpp) on models built
+"""The set-packing solver (rgc_ilp.hip, ilp_core / ilp_solve_rec of rgc_ilp_host.cpp) on models built
 to put one conflict component on each size at which it takes another path, and on the inputs
 its ABI allows but get_cliques never produces (tests/ilp_models.py).
 

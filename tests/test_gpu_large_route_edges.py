@@ -1,5 +1,5 @@
-"""The large-micrograph route (rgc_kernels.hip, rgc_cliques.hip, run_multi in rgc_abi.cpp) at
-the sizes and degrees where it selects another path, both sides of each:
+"""The large-micrograph route (rgc_kernels.hip, rgc_cliques.hip, run_multi in rgc_run_large.cpp)
+at the sizes and degrees where it selects another path, both sides of each:
 
 * a valid picker-0 root of more than RB_W = 64 forward neighbours sends its micrograph to the
   thread-per-root DFS (k5_cliques<K, FILL>, K = 2..8), whose cliques follow the level route's

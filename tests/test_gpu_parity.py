@@ -371,8 +371,9 @@ def test_gpu_submit_wait_pipelined_contexts(streams):
     """rgc_submit / rgc_wait (ABI 3) on two contexts sharing one stream, or on a stream each
     (bench.py's default: consecutive steps' launches overlap), the bench's pipelined steps:
     every batch's outputs equal rgc_run's.  Batches cover the single-launch fast path, a
-    micrograph that needs the f64 pass (the fast path falls back at rgc_wait) and a batch with
-    a large micrograph (general path at rgc_submit).  Child process as above."""
+    micrograph that needs the f64 pass (the fast path falls back at rgc_wait), a batch with
+    a large micrograph (general path at rgc_submit) and a fast-path batch of two launch
+    groups.  Child process as above."""
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
@@ -412,6 +413,14 @@ def _submit_wait_check(streams=1):
     big = synth.SynthConfig(k=3, n_true=1800, box=60, width=4096, height=4096, keep=0.9,
                             jit=0.08, fp=0.1, seed=22)
     b3 = Batch.pack(3, 180, synth.batch(cfg, 20, start=400) + synth.batch(big, 1))
+    # small and large micrographs in one fast-path batch: their size classes (about 180 boxes
+    # and about 1500) have plans of different occupancy, so rgc_submit launches them as two
+    # groups over HBM micrograph lists
+    small = synth.SynthConfig(**{**synth.CONFIGS["C2"], "n_true": 60}, seed=23)
+    large = synth.SynthConfig(**{**synth.CONFIGS["C2"], "n_true": 500}, seed=24)
+    sm, lg = synth.batch(small, 6), synth.batch(large, 2)
+    b4 = Batch.pack(3, 180, sm[:3] + lg[:1] + sm[3:] + lg[1:])
+    batches = (b1, b2, b3, b4)
     dev = torch.device("cuda", 0)
     fl = _lib.F_MEMBERS | _lib.F_GET_CC
     per_mg = ("status", "cc_max", "cc_cnt", "n_vert", "clique_cnt")
@@ -432,7 +441,7 @@ def _submit_wait_check(streams=1):
 
     ref_ctx = _lib.Context(0)
     refs, dev_in = [], []
-    for b in (b1, b2, b3):
+    for b in batches:
         refs.append(snap(ref_ctx.run(b.n_mg, 3, 180, b.box_off, b.id_base, b.x, b.y, b.score,
                                      fl | _lib.F_HOST_OUTPUTS), False))
         t = [torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (b.x, b.y, b.score)]
@@ -447,7 +456,7 @@ def _submit_wait_check(streams=1):
     def submit(c, i, lazy=False):
         # lazy: ABI 6 F_LAZY_STATS (the bench's steps): per-micrograph outputs fetched from HBM
         # when the Result first reads them
-        b, t = (b1, b2, b3)[i], dev_in[i]
+        b, t = batches[i], dev_in[i]
         c.submit(b.n_mg, 3, 180, b.box_off, b.id_base, t[0].data_ptr(), t[1].data_ptr(),
                  t[2].data_ptr(), fl | _lib.F_DEVICE_INPUTS | _lib.F_TIMING |
                  (_lib.F_LAZY_STATS if lazy else 0),
@@ -471,11 +480,13 @@ def _submit_wait_check(streams=1):
             assert "awaits rgc_wait" in str(e)
     ctxs[0].wait()
 
-    order = [0, 1, 2, 0, 2, 1, 0, 1, 0]
+    # (each step of batch 3 follows one of batch 0 on its context, so no device-side f64 pass
+    # adds a launch to it: its launches are its groups)
+    order = [0, 1, 2, 0, 3, 2, 1, 0, 1, 0, 0, 3]
     submit(ctxs[0], order[0])
     for j, i in enumerate(order):
         if j + 1 < len(order):
-            submit(ctxs[(j + 1) % 2], order[j + 1], lazy=j + 1 >= 6)
+            submit(ctxs[(j + 1) % 2], order[j + 1], lazy=j + 1 >= 7)
         got = snap(ctxs[j % 2].wait(), True)
         for f in per_mg:
             np.testing.assert_array_equal(got[f], refs[i][f], err_msg=f"{f} batch {i}")
@@ -483,7 +494,14 @@ def _submit_wait_check(streams=1):
         for f, _, _ in per_cl:
             for a, e in zip(got[f], refs[i][f]):
                 np.testing.assert_array_equal(a.view(np.uint8), e.view(np.uint8), err_msg=f)
-        assert any(n == "k_fused" for n, _ in ctxs[j % 2].kernel_times())
+        names = [n for n, _ in ctxs[j % 2].kernel_times()]
+        assert "k_fused" in names
+        if i in (0, 3):
+            # the fast path from submit to wait (only the general path records "d2h_stats"):
+            # a section per launch, then the ties kernel
+            n_launch = len(names) - 1
+            assert n_launch >= (2 if i == 3 else 1), names
+            assert names == ["k_fused"] * n_launch + ["k_fused_ties"], names
     for c in ctxs + [ref_ctx]:
         c.close()
 

@@ -36,7 +36,7 @@ from repic_amd import synth  # noqa: E402
 from stencil_check import plan  # noqa: E402
 
 f32 = np.float32
-# the workgroup size the host picks for the bench configs (rgc_abi.cpp: plan_fused)
+# the workgroup size the host picks for the bench configs (rgc_run.cpp: plan_fused)
 DEFAULT_THREADS = {"C2": 512, "C3": 1024, "C4": 768, "C5": 1024}
 
 
