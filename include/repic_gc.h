@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RGC_ABI_VERSION 10
+#define RGC_ABI_VERSION 11
 
 /* flags for rgc_batch_in.flags */
 #define RGC_F_GET_CC         1u  /* --get_cc   (get_cliques.py:151-156) */
@@ -52,8 +52,11 @@ extern "C" {
                                   * takes the single fused launch stay in HBM; rgc_wait copies
                                   * only the run's totals and rgc_fetch_stats copies the rest
                                   * (outputs kept in HBM, like RGC_F_HOST_OUTPUTS unset) */
-#define RGC_F_EDGES        256u  /* test hook: also record every JI > 0.3 edge with its f64 JI
-                                    (rgc_last_edges); outputs are unchanged */
+#define RGC_F_EDGES        256u  /* test hook: also record every JI > threshold edge with its
+                                    f64 JI (rgc_last_edges); outputs are unchanged */
+#define RGC_F_JI_THRESHOLD 1024u /* ABI 11: rgc_batch_in.ji_threshold holds the Jaccard threshold
+                                  * (else 0.3, and the field is not read: a caller built against
+                                  * the earlier struct layout works unchanged) */
 
 /* per-micrograph status (rgc_batch_out.status) */
 #define RGC_OK          0   /* outputs written as in get_cliques.py:215-229 */
@@ -76,6 +79,11 @@ typedef struct rgc_batch_in {
   const double* score;     /* [N] score, sigmoid already applied on host (common.py:92-94) */
   const int32_t* dev_box_off;  /* DEVICE [n_mg*k+1], int32 copy of box_off (RGC_F_DEVICE_META) */
   const int64_t* dev_id_base;  /* DEVICE [n_mg], copy of id_base (RGC_F_DEVICE_META) */
+  double ji_threshold;     /* ABI 11, read only with RGC_F_JI_THRESHOLD: two boxes of different
+                              pickers are joined when the reference's f64 JI (get_cliques.py
+                              :40-46) exceeds it (get_jaccard's `threshold`, :59-69; the
+                              reference passes 0.3, :138).  Finite, 0 <= t < 1, else rgc_run /
+                              rgc_submit / rgc_consensus fail before any launch */
 } rgc_batch_in;
 
 typedef struct rgc_batch_out {
@@ -86,7 +94,7 @@ typedef struct rgc_batch_out {
   int32_t* cc_cnt;         /* runtime.tsv column 3 */
   int32_t* n_nodes;        /* graph nodes (boxes with >= 1 edge) */
   int32_t* n_vert;         /* constraint-matrix rows V (get_cliques.py:164) */
-  int64_t* n_edges_mg;     /* JI > 0.3 edges */
+  int64_t* n_edges_mg;     /* JI > threshold edges */
   int64_t* clique_base;    /* cliques of mg m are [clique_base[m], +clique_cnt[m]) in the */
   int64_t* clique_cnt;     /* per-clique arrays (ranges of different micrographs do not
                               overlap; their order is unspecified) */
@@ -161,8 +169,8 @@ void rgc_host_block_free(void* block);
 /* Per-kernel device milliseconds of the last rgc_run with RGC_F_TIMING; returns the count. */
 int rgc_kernel_times(rgc_ctx* ctx, int max_n, float* ms, const char** names);
 
-/* Test hook (RGC_F_EDGES): the JI > 0.3 edges of the last rgc_run as host arrays (batch box
- * indices u < v by picker, JI in the reference's f64 op order, get_cliques.py:40-46,59-69),
+/* Test hook (RGC_F_EDGES): the JI > threshold edges of the last rgc_run as host arrays (batch
+ * box indices u < v by picker, JI in the reference's f64 op order, get_cliques.py:40-46,59-69),
  * valid until the next rgc_run; returns the edge count (order unspecified). */
 int64_t rgc_last_edges(rgc_ctx* ctx, const int32_t** u, const int32_t** v, const double** ji);
 
@@ -357,6 +365,13 @@ int rgc_write_boxes(const rgc_box_write_in* in, int n_threads, int64_t* failed_m
  * least two digits; returns the length. */
 int rgc_np_float_str(float v, char* buf, int cap);
 
+/* Host test hook (ABI 11): what the launches pass for box_size and threshold t.  An edge is
+ * I > *int_cut on the integer layout (I the integer overlap area) and I > *f64_hi on the f64
+ * layout; *f64_lo == *f64_hi, the largest f64 I whose reference quotient I / (2 B^2 - I) does
+ * not exceed t (no band of undecided areas is left between them).  Returns 0, or a negative
+ * code for box_size outside 1..2^26 or t outside [0, 1). */
+int rgc_test_ji_cutoff(int64_t box_size, double t, int64_t* int_cut, double* f64_lo,
+                       double* f64_hi);
 /* Host test hooks for the CPython set-order emulation (pyset.h). */
 uint64_t rgc_py_hash_node(double x, double y, int64_t id);
 int rgc_py_set_order(const uint64_t* hashes, int n, int8_t* out);

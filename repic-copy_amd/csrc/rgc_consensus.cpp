@@ -143,7 +143,7 @@ int rgc_consensus(rgc_ctx* c, const rgc_batch_in* in, const rgc_consensus_opts* 
   HIPCHK(hipSetDevice(c->device));
   c->lazy_n_mg = -1;
   std::memset(out, 0, sizeof(*out));
-  rgc_batch_in bi = *in;
+  rgc_batch_in bi = batch_copy(in);
   bi.flags |= opts->flags & RGC_F_TIMING;
   bi.flags &= ~(uint32_t)RGC_F_LAZY_STATS;
   if (!(bi.flags & RGC_F_TIMING)) {

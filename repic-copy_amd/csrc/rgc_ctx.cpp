@@ -119,6 +119,17 @@ int rgc_abi_version(void) { return RGC_ABI_VERSION; }
 
 const char* rgc_last_error(void) { return g_err.c_str(); }
 
+int rgc_test_ji_cutoff(int64_t box_size, double t, int64_t* int_cut, double* f64_lo,
+                       double* f64_hi) {
+  if (!int_cut || !f64_lo || !f64_hi) return fail("null argument");
+  if (box_size < 1 || box_size > (1LL << 26)) return fail("box_size must be in 1..2^26");
+  if (!(t >= 0.0 && t < 1.0)) return fail("ji_threshold must be finite and in [0, 1)");
+  const rgc::JiCut c = rgc::ji_cut(box_size, t);
+  *int_cut = c.int_cut;
+  *f64_lo = *f64_hi = c.f64_cut;
+  return 0;
+}
+
 int rgc_device_count(int* n) {
   HIPCHK(hipGetDeviceCount(n));
   return 0;

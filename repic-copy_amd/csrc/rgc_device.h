@@ -374,12 +374,12 @@ __host__ __device__ __forceinline__ double jaccard(double x, double y, double a,
   return inter / (two_b2 - inter);
 }
 
-// JI > 0.3 test including the |dx| <= B prefilter (get_cliques.py:64-65)
+// JI > t test including the |dx| <= B prefilter (get_cliques.py:64-65)
 __device__ __forceinline__ bool is_edge(double xa, double ya, double xb, double yb, double B,
-                                        double two_b2, double* ji) {
+                                        double two_b2, double t, double* ji) {
   if (!(fabs(xa - xb) <= B)) return false;
   *ji = jaccard(xa, ya, xb, yb, B, two_b2);
-  return *ji > 0.3;
+  return *ji > t;
 }
 
 // Compare-exchange networks on register arrays (fully unrolled: no scratch).  Batcher's

@@ -375,7 +375,7 @@ __device__ __forceinline__ int64_t ufl64(int64_t v) {
 
 // the micrograph's grid geometry, uniform across the workgroup
 struct GridU {
-  double minx, miny, inv_cell, inv_celly;   // columns >= 1.08 B wide, rows >= 0.54 B tall
+  double minx, miny, inv_cell, inv_celly;   // columns >= 2 row_min wide, rows >= row_min tall
   float inv_cellf;                          // (float)inv_cell: P2's half-column test
   float inv_gy;
   int gx, gy, ncell, nkey;
@@ -819,8 +819,8 @@ struct BfsLevel {
     // Candidate walk of an entry: count and 32-bit mask of the valid extensions among dst[lo, hi),
     // the first segment of its last member's list.  An extension h (picker D) must be adjacent to
     // every earlier member: the graph's edges are exactly the pairs of different pickers with
-    // JI > 0.3, so instead of a binary search of h in each member's sorted list (three dependent
-    // LDS loads each), P2's own test on the two boxes' coordinates decides it (ep.edge: the same
+    // JI > threshold, so instead of a binary search of h in each member's sorted list (three
+    // dependent LDS loads each), P2's own test on the two boxes' coordinates decides it (ep.edge: the same
     // function on the same LDS values, so the same answer); the members' coordinates mc stay in
     // registers.
     auto candidates = [&](int lo, int hi, const CT (&mc)[NC], uint32_t& cnt, uint32_t& mask) {
@@ -1152,18 +1152,15 @@ __device__ __forceinline__ double max_f64(double a, double b) {
   return r;
 }
 
-// JI > 0.3 (get_cliques.py:40-46, 64-65): branch-free overlap; the reference quotient is
-// evaluated only inside the ambiguity band [i_lo, i_hi] (rare, divergent)
-__device__ __forceinline__ bool edge_test(double2 a, double2 b, double B, double two_b2,
-                                          double i_lo, double i_hi) {
+// JI > threshold (get_cliques.py:40-46, 64-65): branch-free overlap in the reference's op
+// order, then I > cut, the largest I whose reference quotient does not exceed the threshold
+// (JiCut: the reference's decision for every threshold, without the division)
+__device__ __forceinline__ bool edge_test(double2 a, double2 b, double B, double cut) {
   double xo = (min_f64(a.x, b.x) + B) - max_f64(a.x, b.x);
   double yo = (min_f64(a.y, b.y) + B) - max_f64(a.y, b.y);
   xo = max_f64(xo, 0.0);
   yo = max_f64(yo, 0.0);
-  const double inter = xo * yo;
-  bool e = inter > i_hi;
-  if (!e && inter >= i_lo) e = inter / (two_b2 - inter) > 0.3;   // reference quotient
-  return e;
+  return xo * yo > cut;
 }
 
 // P2's edge decision on two boxes' LDS coordinates (lower picker first), for P4's adjacency
@@ -1172,13 +1169,13 @@ template <bool W>
 struct EdgeP {
   using CT = typename std::conditional<W, double2, float2>::type;
   float Bf, Tf;
-  double B, two_b2, ilo, ihi;
+  double B, cut;
   __device__ __forceinline__ CT pt(const FShared& S, int p) const {
     return reinterpret_cast<const CT*>(S.sxy)[p];
   }
   __device__ __forceinline__ bool edge(CT a, CT b) const {
     if constexpr (W) {
-      return edge_test(a, b, B, two_b2, ilo, ihi);
+      return edge_test(a, b, B, cut);
     } else {
       const float xo = fmaxf(Bf - fabsf(a.x - b.x), 0.0f);
       const float yo = fmaxf(Bf - fabsf(a.y - b.y), 0.0f);
@@ -1195,25 +1192,24 @@ struct EdgeP {
 // too), i.e. the length of the list's first picker segment.
 template <int K, bool W>
 __device__ __forceinline__ int pairs_count(const Stencil& st, const FShared& S, const GridU& H,
-                                           double B, double two_b2, double i_lo, double i_hi,
-                                           Span& g0, Span& g1, uint32_t* mask_out,
+                                           double B, double cut, float rej, Span& g0, Span& g1,
+                                           uint32_t* mask_out,
                                            int* first_out) {
   uint32_t mask = 0, pk = 0;
   int cnt = 0, first = 0;
-  // f32 layout: reject in f32 first.  An edge needs both overlaps > (6/13) B, i.e. |dx| and
-  // |dy| < (7/13) B = 0.5385 B; the f32 difference of two exact f32 values is within 2^-24 of
-  // the true one, so |dx| >= 0.54 B (as computed) can never be an edge.
-  const float rej = 0.54f * (float)B;
+  // f32 layout: reject in f32 first.  An edge needs |dx| and |dy| < rho B (JiCut); the f32
+  // difference of two exact f32 values is within 2^-24 of the true one, so |dx| >= rej =
+  // (float)row_min (0.28 % above rho B) as computed can never be an edge.
   const float ax = (float)st.a.x, ay = (float)st.a.y;
   stencil_walk<K>(st, S, H, g0, g1, [&](int t, int kk) {
     bool e;
     if constexpr (W) {
-      e = edge_test(st.a, ld_xy<W>(S, t), B, two_b2, i_lo, i_hi);
+      e = edge_test(st.a, ld_xy<W>(S, t), B, cut);
     } else {
       const float2 bf = reinterpret_cast<const float2*>(S.sxy)[t];
       e = false;
       if (fabsf(ax - bf.x) < rej && fabsf(ay - bf.y) < rej)
-        e = edge_test(st.a, make_double2((double)bf.x, (double)bf.y), B, two_b2, i_lo, i_hi);
+        e = edge_test(st.a, make_double2((double)bf.x, (double)bf.y), B, cut);
     }
     if (e) {
       ++cnt;
@@ -1226,7 +1222,7 @@ __device__ __forceinline__ int pairs_count(const Stencil& st, const FShared& S, 
   return cnt;
 }
 
-// P2 count on integer coordinates (f32 layout, see P2): exact f32 overlaps, I > floor(6B^2/13)
+// P2 count on integer coordinates (f32 layout, see P2): exact f32 overlaps, I > Tf = int_cut
 template <int K>
 __device__ __forceinline__ int pairs_count_int(const Stencil& st, const FShared& S,
                                                const GridU& H, float Bf, float Tf, Span& g0,
@@ -1258,8 +1254,7 @@ __device__ __forceinline__ int pairs_count_int(const Stencil& st, const FShared&
 template <int K, bool W>
 __device__ __forceinline__ void pairs_fill(const Stencil& st, const FShared& S, const GridU& H,
                                            const Span& g0, const Span& g1, uint32_t mask,
-                                           uint16_t* d, double B, double two_b2, double i_lo,
-                                           double i_hi) {
+                                           uint16_t* d, double B, double cut) {
   int c = 0, kk = 0;
   auto fill_grid = [&](const Span& g) {
     if (kk + g.n <= 32) {
@@ -1274,7 +1269,7 @@ __device__ __forceinline__ void pairs_fill(const Stencil& st, const FShared& S, 
       for (int j = 0; j < g.n; ++j) {
         const int idx = kk + j, t = g.at(j);
         const bool e = idx < 32 ? ((mask >> idx) & 1u) != 0
-                                : edge_test(st.a, ld_xy<W>(S, t), B, two_b2, i_lo, i_hi);
+                                : edge_test(st.a, ld_xy<W>(S, t), B, cut);
         if (e) d[c++] = (uint16_t)t;
       }
     }
@@ -1343,16 +1338,18 @@ constexpr int fused_waves_per_eu(int k, int nt) {
 // after a bounded search (then the workgroup keeps the LDS queue).  There are twice as many
 // slots as workgroups of such a launch can be resident, so the search normally succeeds on
 // its first pass; every claimed slot is released by its workgroup before it ends.
-__device__ int qg_claim(const FusedArgs& A) {
-  const int nw = A.qg_nslots >> 5;
+// (the two arguments it reads, not the launch's argument block: a reference to that would keep
+// a copy of the whole block in scratch wherever this call is not inlined)
+__device__ int qg_claim(uint32_t* qg_slots, int qg_nslots) {
+  const int nw = qg_nslots >> 5;
   const int w0 = (int)(blockIdx.x % (unsigned)max(nw, 1));
   for (int pass = 0; pass < 4; ++pass) {
     for (int i = 0; i < nw; ++i) {
       const int wd = (w0 + i) % nw;
-      uint32_t v = __hip_atomic_load(A.qg_slots + wd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      uint32_t v = __hip_atomic_load(qg_slots + wd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       for (int t = 0; t < 32 && v != 0xFFFFFFFFu; ++t) {
         const int b = __builtin_ctz(~v);
-        const uint32_t old = atomicOr(A.qg_slots + wd, 1u << b);
+        const uint32_t old = atomicOr(qg_slots + wd, 1u << b);
         if (!(old & (1u << b))) return wd * 32 + b;
         v = old | (1u << b);
       }
@@ -1514,16 +1511,17 @@ void k_fused(FusedArgs A) {
   STOP_AFTER(0);
   STAMP(1);
   // ---- P1: one grid per picker (x-major cells, K * gx * gy <= 4 nmax + 4 cells in all) and
-  // an LDS counting sort of the boxes by (picker, cell).  JI > 0.3 implies I > (6/13) B^2 and
-  // so |dx|, |dy| < (7/13) B = 0.5385 B: with cells >= 1.08 B wide and >= 0.54 B tall every
-  // edge partner lies in the box's own column or the neighbouring column on the side of the
-  // box's half of its column (its x is within 0.4986 columns), three rows around its row: a
+  // an LDS counting sort of the boxes by (picker, cell).  JI > t implies |dx|, |dy| < rho B,
+  // rho = (1 - t) / (1 + t) (t = 0.3: I > (6/13) B^2, (7/13) B = 0.5385 B): with cells >=
+  // 2 row_min wide and >= row_min tall (row_min = r B, r >= 1.0028 rho, JiCut; 0.54 B at 0.3)
+  // every edge partner lies in the box's own column or the neighbouring column on the side of
+  // the box's half of its column (its x is within 0.4986 columns), three rows around its row: a
   // 2x3 stencil, i.e. two contiguous position ranges per grid.  Per-picker grids let a box
   // visit the boxes of higher pickers only.
   // Wave 0 alone reduces the per-wave bounding boxes and plans the grid (wave-uniform work:
   // done by every wave it cost ~8x its VALU); the other waves read the plan from the header
   // after one barrier.  Planned in f32 with hardware reciprocals: exactness is not needed,
-  // only cells >= 1.08 B x 0.54 B (0.28 % above what an edge needs, far above f32 rounding;
+  // only cells >= 2 row_min x row_min (0.28 % above what an edge needs, far above f32 rounding;
   // the half-column test has 0.0014 columns of slack), K gx gy within the budget (checked on
   // the integers used), and one inv_cell / inv_celly used by every key.
   __syncthreads();
@@ -1546,7 +1544,7 @@ void k_fused(FusedArgs A) {
         const int budget = (fused_cells(A.nmax) + 4) / K;
         const float fex = (float)ex, fey = (float)ey, rb = __builtin_amdgcn_rcpf((float)budget);
         // row height h, column width 2 h
-        float fch = fmaxf((float)(0.54 * A.B) * 1.000001f,
+        float fch = fmaxf((float)A.cut.row_min * 1.000001f,
                           fmaxf(__builtin_sqrtf(0.5f * fex * fey * rb),
                                 fmaxf(0.5f * fex, fey) * rb));
         for (;;) {
@@ -1561,9 +1559,9 @@ void k_fused(FusedArgs A) {
         cl = (double)fch;
         icly = (double)__builtin_amdgcn_rcpf(fch);
         icl = 0.5 * icly;
-        // keys use icl / icly: columns must stay >= 1.08 B wide, rows >= 0.54 B tall
-        if (icl * (1.08 * A.B) > 1.0) icl = 1.0 / (1.08 * A.B);
-        if (icly * (0.54 * A.B) > 1.0) icly = 1.0 / (0.54 * A.B);
+        // keys use icl / icly: columns must stay >= 2 row_min wide, rows >= row_min tall
+        if (icl * (2.0 * A.cut.row_min) > 1.0) icl = 1.0 / (2.0 * A.cut.row_min);
+        if (icly * A.cut.row_min > 1.0) icly = 1.0 / A.cut.row_min;
       }
     }
     if (tid == 0) {
@@ -1677,19 +1675,19 @@ void k_fused(FusedArgs A) {
   // ---- P2: Jaccard pairs (forward edges to higher pickers): count (JI test, edge bitmask
   // per box) and list write in one pass, lists sorted as written.
   const double B = A.B, two_b2 = A.two_b2;
-  // JI > 0.3  <=>  I > (6/13) B^2 exactly; decide without the division unless I lies within a
-  // 2^-40 relative band of the threshold, where the reference's f64 quotient is evaluated.
-  // Outside the band the quotient's two roundings (< 3e-16 relative) cannot cross 0.3 (the
-  // band moves the quotient by >= 1.1e-12 relative), so the decision is the reference's.
-  const double t_star = 0.6 * B * B / 1.3;
-  const double i_lo = t_star * (1.0 - 0x1p-40), i_hi = t_star * (1.0 + 0x1p-40);
+  // JI > t  <=>  I > cut, the largest f64 I whose reference quotient fl(I / fl(2 B^2 - I))
+  // does not exceed t: the quotient is monotone in I, so the host's bisection (JiCut) makes
+  // the comparison the reference's decision for every t, without the division.
+  // (both taken out of the argument tuple like c.B above: they stay live through P4)
+  const double cut = sdetach(A.cut.f64_cut);
   // f32 layout = integer coordinates (|v| < 2^23) and an integer 1 <= B <= 2896: the overlaps B - |dx| and
-  // their product (< 2^24) are exact in f32 and JI > 0.3 <=> I > floor(6 B^2 / 13) (at
-  // I = 6 B^2 / 13 the reference's quotient rounds to 0.3 itself, not above it), so the count
-  // pass decides every candidate with six f32 operations (edge_test_int)
+  // their product (< 2^24) are exact in f32 and JI > t <=> I > int_cut, the same bisection over
+  // the integers (t = 0.3: floor(6 B^2 / 13); at I = 6 B^2 / 13 the reference's quotient rounds
+  // to 0.3 itself, not above it), so the count pass decides every candidate with six f32
+  // operations (pairs_count_int)
   // (the f32 layout is integer-only: P0)
-  const int ti = W ? 0 : (6 * (int)B * (int)B) / 13;
-  const EdgeP<W> ep{(float)B, (float)ti, B, two_b2, i_lo, i_hi};   // (P4's adjacency tests)
+  const float Tf = __int_as_float(sdetach(__float_as_int(A.cut.tf)));
+  const EdgeP<W> ep{(float)B, Tf, B, cut};   // (P4's adjacency tests: P2's values)
   // thread per box (sorted position): lanes of a wave hold neighbouring boxes of one picker,
   // so their stencils overlap (similar trip counts, broadcast LDS reads), and the waves of
   // picker K-1 have nothing to do.
@@ -1718,8 +1716,8 @@ void k_fused(FusedArgs A) {
       if (act) {
         stencil_setup<K, W>(st, ts, S, G);
         if constexpr (!W)
-          ec = pairs_count_int<K>(st, S, G, (float)B, (float)ti, g0, g1, &mask, &ec1);
-        else ec = pairs_count<K, W>(st, S, G, B, two_b2, i_lo, i_hi, g0, g1, &mask, &ec1);
+          ec = pairs_count_int<K>(st, S, G, (float)B, Tf, g0, g1, &mask, &ec1);
+        else ec = pairs_count<K, W>(st, S, G, B, cut, (float)A.cut.row_min, g0, g1, &mask, &ec1);
       }
       const bool top = (ts & 63) == 63;   // the lane that writes the block's end
       // (lanes past the last box store too: fwd[n] is the end of box n - 1's list unless that
@@ -1750,7 +1748,7 @@ void k_fused(FusedArgs A) {
         d[0] = (uint16_t)(ec == 2 ? mask >> 16 : mask);
         if (ec == 2) d[1] = (uint16_t)mask;
       } else {
-        pairs_fill<K, W>(st, S, G, g0, g1, mask, d, B, two_b2, i_lo, i_hi);
+        pairs_fill<K, W>(st, S, G, g0, g1, mask, d, B, cut);
       }
       S.flags[ts] = 1;
     }
@@ -1772,7 +1770,7 @@ void k_fused(FusedArgs A) {
   uint16_t* esrc_g = nullptr;
   if constexpr (QG) {
     if (st2 == 0 && 2 * E > A.ecap && A.qg_base) {
-      if (tid == 0) H.qslot = qg_claim(A);
+      if (tid == 0) H.qslot = qg_claim(A.qg_slots, A.qg_nslots);
       __syncthreads();
       qslot = ufl(H.qslot);
       if (qslot >= 0) esrc_g = reinterpret_cast<uint16_t*>(A.qg_base + (size_t)qslot * A.qg_bytes);
@@ -1980,7 +1978,7 @@ void k_fused(FusedArgs A) {
     // large micrographs: the level trees in an HBM slot (no root chunks to re-walk), the
     // LDS region when no slot is free (P2 may have claimed the slot already for esrc)
     if (qslot < 0) {
-      if (tid == 0) H.qslot = A.qg_base ? qg_claim(A) : -1;
+      if (tid == 0) H.qslot = A.qg_base ? qg_claim(A.qg_slots, A.qg_nslots) : -1;
       __syncthreads();
       qslot = ufl(H.qslot);
     }

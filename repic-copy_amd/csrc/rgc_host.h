@@ -146,8 +146,15 @@ inline T* H(rgc_ctx* c, int id) { return reinterpret_cast<T*>(c->h[id].p); }
 
 // ---- the routes (rgc_run.cpp, rgc_run_large.cpp, rgc_ilp_host.cpp)
 int run_impl(rgc_ctx* c, const rgc_batch_in* in, rgc_batch_out* out);
+// A batch descriptor as its own copy.  ji_threshold is appended to the struct (ABI 11) and read
+// only under RGC_F_JI_THRESHOLD: a caller built against the earlier layout passes a shorter
+// struct, so the copy takes the earlier layout's bytes and the field only with the flag.
+rgc_batch_in batch_copy(const rgc_batch_in* in);
+// The batch's Jaccard threshold (0.3 without the flag); false: not a finite value in [0, 1)
+bool batch_threshold(const rgc_batch_in* in, double* t);
 // the multi-kernel pipeline on a (sub-)batch of device arrays (rgc_run_large.cpp)
-int run_multi(rgc_ctx* c, int n_mg, int k, double B, double two_b2, int get_cc, int multi,
+int run_multi(rgc_ctx* c, int n_mg, int k, double B, double two_b2, const rgc::JiCut& cut,
+              int get_cc, int multi,
               bool want_members, bool want_ji, const int64_t* box_off, const int64_t* id_base,
               const double* x, const double* y, const double* sc, int64_t out_base,
               std::vector<rgc::MgStat>& st_out, int64_t* C_out, int64_t* E_out);

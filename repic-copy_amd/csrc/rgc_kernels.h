@@ -4,6 +4,8 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <cmath>
+#include <cstring>
 
 namespace rgc {
 
@@ -25,7 +27,8 @@ constexpr int MAX_K = 8;            // largest picker count with a compiled cliq
 constexpr int SCAN_TILE = 2048;     // elements per scan workgroup
 
 // Per-picker grids of one micrograph (k1_bin): gx x gy cells per picker, columns `cell` =
-// 1 / inv_cell wide (>= 1.08 B), rows >= 0.54 B tall, keys picker * ncell + cx * gy + cy;
+// 1 / inv_cell wide (>= 2 row_min), rows >= row_min tall (JiCut), keys picker * ncell +
+// cx * gy + cy;
 // nkey = k * ncell (non-finite boxes); flags bit 0: integer layout (exact f32 JI test).
 struct MgGrid {
   double minx, miny, cell, inv_cell, inv_celly;
@@ -37,6 +40,53 @@ __host__ __device__ inline int bin_budget(int64_t n, bool wide) {
   const int64_t cap = wide ? 32760 : 65528;
   return (int)(2 * n + 64 < cap ? 2 * n + 64 : cap);
 }
+
+// The Jaccard threshold t (0 <= t < 1) as the kernels take it: an edge is the reference's f64
+// `I / (2 B^2 - I) > t` (get_cliques.py:59-69), I the overlap area in the reference's op order.
+// The quotient q(I) = fl(I / fl(2 B^2 - I)) is monotone non-decreasing in I (the subtraction
+// and the division are correctly rounded, and rounding is monotone), so for every t there is a
+// largest I with q(I) <= t, and `I > cut` IS the reference's decision: no division and no band
+// around a real-valued threshold whose roundings would have to be argued per t.  ji_cut finds
+// that I by bisection, over the f64 values in [0, B^2] (f64_cut; non-negative doubles order as
+// their bit patterns) and over the integers (int_cut, the integer layout's areas: exact in f32
+// for B <= 2896).  At t = 0.3 int_cut = floor(6 B^2 / 13) for every B in 1..2896.
+// Reach: JI > t needs both overlaps above (2 t / (1 + t)) B, i.e. |dx|, |dy| < rho B with
+// rho = (1 - t) / (1 + t) (7/13 at 0.3, 1 at 0).  Grid rows are at least row_min = r B tall and
+// columns 2 r B wide, r = rho with >= 0.28 % slack, rounded up to 1/100 (0.54 at t = 0.3): the
+// 2 x 3 stencil holds every partner and its half-column test sees rho B / (2 r B) <= 0.4986.
+struct JiCut {
+  double f64_cut;   // edge <=> I > f64_cut (f64 layout, any I)
+  double row_min;   // r B: least row height; least column width = 2 row_min
+  int64_t int_cut;  // edge <=> I > int_cut for integer I
+  float tf;         // (float)int_cut
+};
+inline JiCut ji_cut(int64_t box_size, double t) {
+  JiCut c{};
+  const double B = (double)box_size, b2 = B * B, two_b2 = (double)(2 * box_size * box_size);
+  auto above = [&](double I) { return I / (two_b2 - I) > t; };
+  if (box_size > 0) {
+    int64_t lo = 0, hi = box_size * box_size;   // q(lo) <= t < q(hi) = 1
+    while (hi - lo > 1) {
+      const int64_t mid = lo + (hi - lo) / 2;
+      (above((double)mid) ? hi : lo) = mid;
+    }
+    c.int_cut = lo;
+    uint64_t blo = 0, bhi;
+    std::memcpy(&bhi, &b2, 8);
+    while (bhi - blo > 1) {
+      const uint64_t mid = blo + (bhi - blo) / 2;
+      double v;
+      std::memcpy(&v, &mid, 8);
+      (above(v) ? bhi : blo) = mid;
+    }
+    std::memcpy(&c.f64_cut, &blo, 8);
+  }
+  c.tf = (float)c.int_cut;
+  const double rho = (1.0 - t) / (1.0 + t);
+  c.row_min = (std::ceil(rho * 1.0028 * 100.0) / 100.0) * B;
+  return c;
+}
+constexpr double JI_DEFAULT = 0.3;   // the reference's one call site (get_cliques.py:138)
 
 // Per-micrograph results.
 struct MgStat {
@@ -96,6 +146,7 @@ constexpr int STAMP_SLOTS = 16 + 13 * 16;
 struct FusedArgs {
   int k, flags;                 // flags: bit0 get_cc, bit1 multi_out, bit5 members
   double B, two_b2;
+  JiCut cut;                    // the edge threshold (uniform launch argument)
   int nmax, ecap;               // LDS capacities of this launch (boxes, forward edges)
   const int32_t* mg_list;       // micrographs of this launch (nullptr: block b = micrograph b)
   const int32_t* box_off;
@@ -120,8 +171,8 @@ struct FusedArgs {
   int32_t* members;
   uint8_t* order;
   unsigned long long* stamps;   // diagnostic build (RGC_STAMPS) only: STAMP_SLOTS per WG
-  // RGC_F_EDGES test hook (nullptr otherwise): every JI > 0.3 edge as (u, v, JI) with batch
-  // box indices, reserved per micrograph on cursor[2]; nothing is written past ecap_out
+  // RGC_F_EDGES test hook (nullptr otherwise): every JI > threshold edge as (u, v, JI) with
+  // batch box indices, reserved per micrograph on cursor[2]; nothing is written past ecap_out
   int32_t* eu;
   int32_t* ev;
   double* eji;
@@ -220,13 +271,14 @@ struct CliqueArgs {
 };
 
 
-void launch_bin(hipStream_t stream, int n_mg, int k, double B, const int32_t* box_off,
+void launch_bin(hipStream_t stream, int n_mg, int k, double B, double row_min,
+                const int32_t* box_off,
                 const int32_t* cell_off, const double* x, const double* y, MgGrid* grid,
                 int32_t* cell_start, double* sx, double* sy, int32_t* sbox, uint8_t* spick,
                 int32_t* smg, int32_t* bmg, uint8_t* bpick, bool wide, int max_n);
 void launch_pairs(hipStream_t stream, bool fill, int N, int k, double B, double two_b2,
-                  const int32_t* box_off, const int32_t* cell_off, const MgGrid* grid,
-                  const int32_t* cell_start, const double* sx, const double* sy,
+                  const JiCut& cut, const int32_t* box_off, const int32_t* cell_off,
+                  const MgGrid* grid, const int32_t* cell_start, const double* sx, const double* sy,
                   const int32_t* sbox, const uint8_t* spick, const int32_t* smg,
                   int32_t* fwd_cnt, const int64_t* fwd_off, int32_t* e_dst, double* e_ji);
 // up to 16 memsets in one launch (k_fill_multi): pointers 16-byte aligned

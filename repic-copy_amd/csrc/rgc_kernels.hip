@@ -4,7 +4,7 @@
 // see DESIGN.md §3).  Reference functions replaced (reference repic/commands/get_cliques.py):
 //   k1_bin            spatial grid (cell >= box_size) so the O(n_a*n_b) pair loop (:59-69)
 //                     becomes a 3x3 cell stencil
-//   k2_pairs<FILL>    calc_jaccard (:40-46) + |dx| <= B prefilter + JI > 0.3 (:64-65,:138),
+//   k2_pairs<FILL>    calc_jaccard (:40-46) + |dx| <= B prefilter + JI > t (:64-65,:138),
 //                     two-phase count -> scan -> fill; forward CSR sorted by target box
 //   k4_*              nx.connected_components stats (:145-149), --get_cc (:151-156)
 //   k5_cliques<K,..>  find_cliques (:49-56) for micrographs with a root of more than RB_W
@@ -31,9 +31,10 @@ namespace rgc {
 
 // ----------------------------------------------------------------------------- K1 bin
 // Per-picker grids (the fused kernel's P1 restated for whole-GPU kernels): every picker gets
-// its own gx x gy grid of cells >= 1.08 B wide and >= 0.54 B tall over the micrograph's
+// its own gx x gy grid of cells >= 2 row_min wide and >= row_min tall over the micrograph's
 // bounding box, keys picker * ncell + (cx * gy + cy) (x-major), the non-finite boxes in key
-// nkey = K * ncell.  JI > 0.3 needs I > (6/13) B^2, i.e. |dx|, |dy| < (7/13) B = 0.5385 B, so
+// nkey = K * ncell.  JI > t needs |dx|, |dy| < rho B, rho = (1 - t) / (1 + t), and row_min is
+// rho B with >= 0.28 % slack (JiCut; t = 0.3: (7/13) B = 0.5385 B against 0.54 B), so
 // an edge partner lies within 0.4986 columns: in the box's own column or the neighbouring
 // one on the side of the box's half of its column, and within one row: a 2 x 3 stencil = two
 // contiguous position ranges per higher picker's grid (forward edges only).  Keys and the
@@ -51,7 +52,8 @@ __device__ __forceinline__ int bin_key(const MgGrid& G, int p, double x, double 
 // LDS counting sort of the boxes by key.  cell_start[cell_off[m] + key] = first sorted
 // position (local to the micrograph) of each key; entry nkey + 1 = n.
 template <bool WIDE>
-__global__ __launch_bounds__(1024) void k1_bin(int k, double B, const int32_t* __restrict__ box_off,
+__global__ __launch_bounds__(1024) void k1_bin(int k, double B, double row_min,
+                                               const int32_t* __restrict__ box_off,
                                                const int32_t* __restrict__ cell_off,
                                                const double* __restrict__ x,
                                                const double* __restrict__ y, MgGrid* grid,
@@ -96,9 +98,9 @@ __global__ __launch_bounds__(1024) void k1_bin(int k, double B, const int32_t* _
         // beyond the exactness range of the stencil argument: one cell per picker, all pairs
         g.gx = 1; g.gy = 1;
       } else {
-        // row height h, column width 2 h (>= 1.08 B x 0.54 B), k gx gy <= budget
+        // row height h, column width 2 h (>= 2 row_min x row_min), k gx gy <= budget
         const int per = budget / k;
-        double h = fmax(0.54 * B * (1.0 + 1e-9), fmax(sqrt(0.5 * ex * ey / per),
+        double h = fmax(row_min * (1.0 + 1e-9), fmax(sqrt(0.5 * ex * ey / per),
                                                      fmax(0.5 * ex, ey) / per));
         for (;;) {
           const double fx = floor(ex / (2.0 * h)) + 1.0, fy = floor(ey / h) + 1.0;
@@ -108,8 +110,8 @@ __global__ __launch_bounds__(1024) void k1_bin(int k, double B, const int32_t* _
         g.cell = 2.0 * h;
         g.inv_cell = 1.0 / (2.0 * h);
         g.inv_celly = 1.0 / h;
-        if (g.inv_cell * (1.08 * B) > 1.0) g.inv_cell = 1.0 / (1.08 * B);
-        if (g.inv_celly * (0.54 * B) > 1.0) g.inv_celly = 1.0 / (0.54 * B);
+        if (g.inv_cell * (2.0 * row_min) > 1.0) g.inv_cell = 1.0 / (2.0 * row_min);
+        if (g.inv_celly * row_min > 1.0) g.inv_celly = 1.0 / row_min;
       }
       g.ncell = g.gx * g.gy;
       g.nkey = k * g.ncell;
@@ -179,14 +181,16 @@ __global__ __launch_bounds__(1024) void k1_bin(int k, double B, const int32_t* _
 // ----------------------------------------------------------------------------- K2 pairs
 // One thread per box (sorted position, so neighbouring threads share stencil cells in L1/L2):
 // the 2 x 3 stencil (see K1) in the grid of every HIGHER picker.  Integer micrographs decide
-// JI > 0.3 exactly on f32 (overlaps B - |dx| and their product < 2^24 are exact: I >
-// floor(6 B^2 / 13), the fused kernel's P2 test); others test I > (6/13) B^2 in f64 and
-// evaluate the reference quotient (get_cliques.py:40-46) only inside a 2^-40 relative band of
-// the threshold.  COUNT: forward-edge count per box.  FILL: write the targets (and, for the
+// JI > threshold exactly on f32 (overlaps B - |dx| and their product < 2^24 are exact: I >
+// Tf = int_cut, the fused kernel's P2 test); others test I > cut on the reference's f64 area
+// (get_cliques.py:40-46), the largest I whose reference quotient does not exceed the threshold
+// (JiCut: exact for every threshold).
+// COUNT: forward-edge count per box.  FILL: write the targets (and, for the
 // RGC_F_EDGES hook only, the reference JI) into the box's CSR slot, sorted by target box index
 // (picker-major, file order) for the clique intersections.
 template <bool FILL>
 __global__ __launch_bounds__(WG) void k2_pairs(int N, int k, double B, double two_b2,
+                                               float Tf, double cut,
                                                const int32_t* __restrict__ box_off,
                                                const int32_t* __restrict__ cell_off,
                                                const MgGrid* __restrict__ grid,
@@ -225,10 +229,8 @@ __global__ __launch_bounds__(WG) void k2_pairs(int N, int k, double B, double tw
     const int b0 = box_off[m * k];
     const int32_t* cs = cell_start + cell_off[m];
     const bool intl = (G.flags & 1) != 0;
-    const float Bf = (float)B, Tf = (float)((6 * (int64_t)B * (int64_t)B) / 13);
+    const float Bf = (float)B;
     const float axf = (float)xa, ayf = (float)ya;
-    const double t_star = 0.6 * B * B / 1.3;
-    const double i_lo = t_star * (1.0 - 0x1p-40), i_hi = t_star * (1.0 + 0x1p-40);
     for (int q = p + 1; q < k; ++q) {
       int rk[FILL_REGS];
 #pragma unroll
@@ -250,9 +252,7 @@ __global__ __launch_bounds__(WG) void k2_pairs(int N, int k, double B, double tw
           } else {
             const double xo = fmax((fmin(xa, xb) + B) - fmax(xa, xb), 0.0);
             const double yo = fmax((fmin(ya, yb) + B) - fmax(ya, yb), 0.0);
-            const double inter = xo * yo;
-            e = inter > i_hi;
-            if (!e && inter >= i_lo) e = inter / (two_b2 - inter) > 0.3;   // reference quotient
+            e = xo * yo > cut;
           }
           if (e) {
             if (FILL) {
@@ -937,7 +937,8 @@ void launch_remap(hipStream_t stream, int64_t C, int k, const int32_t* orig, int
 #define RGC_LAUNCH(kern, grid, block, ...) \
   hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, stream, __VA_ARGS__)
 
-void launch_bin(hipStream_t stream, int n_mg, int k, double B, const int32_t* box_off,
+void launch_bin(hipStream_t stream, int n_mg, int k, double B, double row_min,
+                const int32_t* box_off,
                 const int32_t* cell_off, const double* x, const double* y, MgGrid* grid,
                 int32_t* cell_start, double* sx, double* sy, int32_t* sbox, uint8_t* spick,
                 int32_t* smg, int32_t* bmg, uint8_t* bpick, bool wide, int max_n) {
@@ -949,29 +950,29 @@ void launch_bin(hipStream_t stream, int n_mg, int k, double B, const int32_t* bo
   if (wide) {
     static std::atomic<uint64_t> attr{0};
     (void)set_dyn_lds_once(attr, reinterpret_cast<const void*>(&k1_bin<true>), 132 * 1024);
-    hipLaunchKernelGGL(k1_bin<true>, dim3(n_mg), dim3(1024), lds, stream, k, B, box_off,
-                       cell_off, x, y, grid, cell_start, sx, sy, sbox, spick, smg, bmg, bpick);
+    hipLaunchKernelGGL(k1_bin<true>, dim3(n_mg), dim3(1024), lds, stream, k, B, row_min,
+                       box_off, cell_off, x, y, grid, cell_start, sx, sy, sbox, spick, smg, bmg, bpick);
   } else {
     static std::atomic<uint64_t> attr{0};
     (void)set_dyn_lds_once(attr, reinterpret_cast<const void*>(&k1_bin<false>), 132 * 1024);
-    hipLaunchKernelGGL(k1_bin<false>, dim3(n_mg), dim3(1024), lds, stream, k, B, box_off,
-                       cell_off, x, y, grid, cell_start, sx, sy, sbox, spick, smg, bmg, bpick);
+    hipLaunchKernelGGL(k1_bin<false>, dim3(n_mg), dim3(1024), lds, stream, k, B, row_min,
+                       box_off, cell_off, x, y, grid, cell_start, sx, sy, sbox, spick, smg, bmg, bpick);
   }
 }
 
 void launch_pairs(hipStream_t stream, bool fill, int N, int k, double B, double two_b2,
-                  const int32_t* box_off, const int32_t* cell_off, const MgGrid* grid,
-                  const int32_t* cell_start, const double* sx, const double* sy,
+                  const JiCut& cut, const int32_t* box_off, const int32_t* cell_off,
+                  const MgGrid* grid, const int32_t* cell_start, const double* sx, const double* sy,
                   const int32_t* sbox, const uint8_t* spick, const int32_t* smg,
                   int32_t* fwd_cnt, const int64_t* fwd_off, int32_t* e_dst, double* e_ji) {
   const int nb = (N + WG - 1) / WG;
   if (nb == 0) return;
   if (fill)
-    RGC_LAUNCH(k2_pairs<true>, nb, WG, N, k, B, two_b2, box_off, cell_off, grid, cell_start, sx,
-               sy, sbox, spick, smg, fwd_cnt, fwd_off, e_dst, e_ji);
+    RGC_LAUNCH(k2_pairs<true>, nb, WG, N, k, B, two_b2, cut.tf, cut.f64_cut, box_off, cell_off,
+               grid, cell_start, sx, sy, sbox, spick, smg, fwd_cnt, fwd_off, e_dst, e_ji);
   else
-    RGC_LAUNCH(k2_pairs<false>, nb, WG, N, k, B, two_b2, box_off, cell_off, grid, cell_start,
-               sx, sy, sbox, spick, smg, fwd_cnt, fwd_off, e_dst, e_ji);
+    RGC_LAUNCH(k2_pairs<false>, nb, WG, N, k, B, two_b2, cut.tf, cut.f64_cut, box_off, cell_off,
+               grid, cell_start, sx, sy, sbox, spick, smg, fwd_cnt, fwd_off, e_dst, e_ji);
 }
 
 // tile buffer words: the one-pass scan's claim counter + one state per tile

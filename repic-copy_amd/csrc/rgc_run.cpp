@@ -190,7 +190,20 @@ struct BatchShape {
   int64_t N = 0;                         // boxes in the batch
   int64_t nmin = INT64_MAX, nmaxb = 0;   // boxes of the smallest / the largest micrograph
   bool get_cc = false, multi = false, want_members = false, want_edges = false;
+  JiCut cut{};                           // the batch's edge threshold as the launches take it
 };
+
+rgc_batch_in batch_copy(const rgc_batch_in* in) {
+  rgc_batch_in c{};
+  std::memcpy(&c, in, offsetof(rgc_batch_in, ji_threshold));
+  if (in->flags & RGC_F_JI_THRESHOLD) c.ji_threshold = in->ji_threshold;
+  return c;
+}
+
+bool batch_threshold(const rgc_batch_in* in, double* t) {
+  *t = (in->flags & RGC_F_JI_THRESHOLD) ? in->ji_threshold : JI_DEFAULT;
+  return *t >= 0.0 && *t < 1.0;   // (false for NaN)
+}
 
 static int64_t mg_boxes(const rgc_batch_in* in, int m) {
   return in->box_off[(int64_t)(m + 1) * in->k] - in->box_off[(int64_t)m * in->k];
@@ -204,6 +217,14 @@ static const char* batch_shape(const rgc_batch_in* in, BatchShape* b) {
   if (b->n_mg < 0) return "n_mg < 0";
   if (b->k < 1 || b->k > MAX_K) return "k (number of pickers) must be in 1..8";
   if (in->box_size > (1LL << 26)) return "box_size too large (> 2^26)";
+  double t;
+  if (!batch_threshold(in, &t)) return "ji_threshold must be finite and in [0, 1)";
+  // (ji_cut bisects, ~90 dependent divisions: kept from the last call while the box size and
+  // the threshold stay the same, which is every step of a pipelined run)
+  struct Memo { int64_t box = -1; double t = 0.0; JiCut cut{}; };
+  static thread_local Memo memo;
+  if (memo.box != in->box_size || memo.t != t) memo = {in->box_size, t, ji_cut(in->box_size, t)};
+  b->cut = memo.cut;
   b->N = b->n_mg ? in->box_off[(int64_t)b->n_mg * b->k] : 0;
   if (b->N >= (1LL << 31) - 1) return "too many boxes in one batch (>= 2^31)";
   b->get_cc = (in->flags & RGC_F_GET_CC) != 0;
@@ -255,6 +276,7 @@ static FusedArgs fused_args(rgc_ctx* c, const BatchShape& b, const rgc_batch_in*
   A.flags = (b.get_cc ? 1 : 0) | (b.multi ? 2 : 0) | (b.want_members ? 32 : 0);
   A.B = (double)in->box_size;
   A.two_b2 = (double)(2 * in->box_size * in->box_size);
+  A.cut = b.cut;
   A.box_off = d_bo; A.id_base = d_id;
   A.x = x; A.y = y; A.score = sc; A.o = io.o;
   A.cursor = io.cur; A.cap = c->cap_cliques;
@@ -591,7 +613,7 @@ int Run::deferred_route() {
   std::vector<MgStat> sst;
   int64_t Cm = 0, Em = 0;
   TRY(run_multi(c, ns, k, (double)in->box_size, (double)(2 * in->box_size * in->box_size),
-                b.get_cc, b.multi, b.want_members, b.want_edges, sbo.data(), sid.data(),
+                b.cut, b.get_cc, b.multi, b.want_members, b.want_edges, sbo.data(), sid.data(),
                 x, y, sc, fused_total, sst, &Cm, &Em));
   if (!ident) {
     TRY(mark(c, "k_remap"));
@@ -897,7 +919,9 @@ int rgc_submit(rgc_ctx* c, const rgc_batch_in* in) {
   if (c->pend) return fail("rgc_submit: a submitted run awaits rgc_wait on this context");
   HIPCHK(hipSetDevice(c->device));
   c->lazy_n_mg = -1;
-  c->pin = *in;
+  double t;
+  if (!batch_threshold(in, &t)) return fail("ji_threshold must be finite and in [0, 1)");
+  c->pin = batch_copy(in);
   const int r = submit_fast(c, in);
   if (r < 0) return r;
   c->pend = true;

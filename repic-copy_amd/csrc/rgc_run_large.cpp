@@ -10,7 +10,8 @@ using namespace rgc;
 
 // Runs the multi-kernel pipeline on a (sub-)batch whose x/y/score are device arrays, writing
 // per-clique outputs at [out_base, out_base + C).  Fills st_out[n_mg] (clique_base/cnt set).
-int run_multi(rgc_ctx* c, int n_mg, int k, double B, double two_b2, int get_cc, int multi,
+int run_multi(rgc_ctx* c, int n_mg, int k, double B, double two_b2, const JiCut& cut,
+              int get_cc, int multi,
               bool want_members, bool want_ji, const int64_t* box_off, const int64_t* id_base,
               const double* x, const double* y, const double* sc, int64_t out_base,
               std::vector<MgStat>& st_out, int64_t* C_out, int64_t* E_out) {
@@ -116,12 +117,12 @@ int run_multi(rgc_ctx* c, int n_mg, int k, double B, double two_b2, int get_cc, 
 
   const int32_t* bo = D<int32_t>(c, D_BOXOFF);
   TRY(mark(c, "k1_bin"));
-  launch_bin(s, n_mg, k, B, bo, d_co, x, y, D<MgGrid>(c, D_GRID),
+  launch_bin(s, n_mg, k, B, cut.row_min, bo, d_co, x, y, D<MgGrid>(c, D_GRID),
              D<int32_t>(c, D_CELLSTART), D<double>(c, D_SX), D<double>(c, D_SY),
              D<int32_t>(c, D_SBOX), D<uint8_t>(c, D_SPICK), D<int32_t>(c, D_SMG),
              D<int32_t>(c, D_BMG), D<uint8_t>(c, D_BPICK), bin_wide, max_n);
   TRY(mark(c, "k2_pairs_count"));
-  launch_pairs(s, false, (int)N, k, B, two_b2, bo, d_co, D<MgGrid>(c, D_GRID),
+  launch_pairs(s, false, (int)N, k, B, two_b2, cut, bo, d_co, D<MgGrid>(c, D_GRID),
                D<int32_t>(c, D_CELLSTART), D<double>(c, D_SX), D<double>(c, D_SY),
                D<int32_t>(c, D_SBOX), D<uint8_t>(c, D_SPICK), D<int32_t>(c, D_SMG),
                D<int32_t>(c, D_FWDCNT), nullptr, nullptr, nullptr);
@@ -139,7 +140,7 @@ int run_multi(rgc_ctx* c, int n_mg, int k, double B, double two_b2, int get_cc, 
   TRY(ensure_dev(c, D_ADJG, E * 8));
   if (want_ji) TRY(ensure_dev(c, D_EJI, E * 8));   // (the edge JIs feed the RGC_F_EDGES dump only)
   TRY(mark(c, "k2_pairs_fill"));
-  launch_pairs(s, true, (int)N, k, B, two_b2, bo, d_co, D<MgGrid>(c, D_GRID),
+  launch_pairs(s, true, (int)N, k, B, two_b2, cut, bo, d_co, D<MgGrid>(c, D_GRID),
                D<int32_t>(c, D_CELLSTART), D<double>(c, D_SX), D<double>(c, D_SY),
                D<int32_t>(c, D_SBOX), D<uint8_t>(c, D_SPICK), D<int32_t>(c, D_SMG),
                D<int32_t>(c, D_FWDCNT), D<int64_t>(c, D_FWDOFF), D<int32_t>(c, D_EDST),

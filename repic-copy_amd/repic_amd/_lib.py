@@ -26,6 +26,8 @@ lib = C.CDLL(LIB_PATH)
 F_GET_CC, F_MULTI_OUT, F_DEVICE_INPUTS, F_HOST_OUTPUTS, F_TIMING = 1, 2, 4, 8, 16
 F_MEMBERS, F_NO_FUSED, F_DEVICE_META, F_EDGES = 32, 64, 128, 256
 F_LAZY_STATS = 512   # ABI 6: per-micrograph outputs fetched on first use (rgc_fetch_stats)
+F_JI_THRESHOLD = 1024   # ABI 11: BatchIn.ji_threshold holds the Jaccard threshold (else 0.3)
+JI_DEFAULT = 0.3   # the reference's threshold (get_cliques.py:138)
 OK, NO_EDGES, NO_CLIQUES = 0, 1, 2
 PARSE_OK, PARSE_INDEX, PARSE_VALUE, PARSE_ASSERT, PARSE_FALLBACK, PARSE_OSERROR = range(6)
 MAX_K = 8
@@ -41,7 +43,8 @@ class BatchIn(C.Structure):
     _fields_ = [("n_mg", C.c_int32), ("k", C.c_int32), ("box_size", C.c_int64),
                 ("flags", C.c_uint32), ("box_off", C.c_void_p), ("id_base", C.c_void_p),
                 ("x", C.c_void_p), ("y", C.c_void_p), ("score", C.c_void_p),
-                ("dev_box_off", C.c_void_p), ("dev_id_base", C.c_void_p)]
+                ("dev_box_off", C.c_void_p), ("dev_id_base", C.c_void_p),
+                ("ji_threshold", C.c_double)]
 
 
 class BatchOut(C.Structure):
@@ -141,13 +144,14 @@ lib.rgc_write_outputs.argtypes = [C.POINTER(PickleFmt), C.POINTER(WriteIn), C.c_
 lib.rgc_pickle_bytes.argtypes = [C.POINTER(PickleFmt), C.POINTER(WriteIn), C.c_int, C.c_int,
                                  C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
 lib.rgc_py_float_repr.argtypes = [C.c_double, C.c_char_p, C.c_int]
+lib.rgc_test_ji_cutoff.argtypes = [C.c_int64, C.c_double, C.POINTER(C.c_int64), _f64p, _f64p]
 
 EXPORTS = ["rgc_abi_version", "rgc_last_error", "rgc_device_count", "rgc_ctx_create",
            "rgc_ctx_destroy", "rgc_ctx_set_copy_stream", "rgc_run", "rgc_submit", "rgc_wait", "rgc_fetch_stats", "rgc_detach_host", "rgc_host_block_free", "rgc_kernel_times", "rgc_last_edges", "rgc_parse_files",
            "rgc_parsed_free", "rgc_py_hash_node", "rgc_py_set_order", "rgc_test_epilogue",
            "rgc_score_pairs", "rgc_ilp_solve", "rgc_write_outputs", "rgc_pickle_bytes",
            "rgc_py_float_repr", "rgc_consensus", "rgc_pick_select", "rgc_write_boxes",
-           "rgc_np_float_str"]
+           "rgc_np_float_str", "rgc_test_ji_cutoff"]
 
 
 class RGCError(RuntimeError):
@@ -168,6 +172,23 @@ def ilp_big_max() -> int:
     """Largest conflict component (cliques) the run_ilp branch and bound searches
     (rgc_ilp.hip ILP_BIG); larger ones are certified, not searched."""
     return 4096
+
+
+def check_ji_threshold(t) -> float:
+    """``t`` as the Jaccard threshold the library accepts (finite, 0 <= t < 1), else ValueError."""
+    t = float(t)
+    if not (0.0 <= t < 1.0):   # (false for nan)
+        raise ValueError(f"ji_threshold must be finite and in [0, 1), got {t!r}")
+    return t
+
+
+def ji_cutoff(box_size: int, t: float):
+    """Test hook (rgc_test_ji_cutoff): (int_cut, f64_lo, f64_hi) the launches pass for
+    ``box_size`` and threshold ``t``: an edge is I > int_cut on the integer layout and
+    I > f64_hi on the f64 layout (f64_lo == f64_hi: no band of undecided areas)."""
+    ic, lo, hi = C.c_int64(0), C.c_double(0), C.c_double(0)
+    _check(lib.rgc_test_ji_cutoff(int(box_size), float(t), C.byref(ic), C.byref(lo), C.byref(hi)))
+    return ic.value, lo.value, hi.value
 
 
 # ----------------------------------------------------------------------------- parsing
@@ -325,15 +346,17 @@ class Context:
             pass
 
     def run(self, n_mg, k, box_size, box_off, id_base, x, y, score, flags=F_HOST_OUTPUTS,
-            dev_meta=None):
+            dev_meta=None, ji_threshold=None):
         """Run the batched pipeline.  ``box_off``/``id_base`` are host int64 arrays;
         ``x``/``y``/``score`` are host float64 arrays, or device pointers (ints) with
         ``F_DEVICE_INPUTS``.  ``dev_meta`` = (device pointer of box_off as int32, device
         pointer of id_base) sets ``F_DEVICE_META``: the offsets are not uploaded per run.
+        ``ji_threshold`` (None: the reference's 0.3) joins two boxes when their JI exceeds it
+        (``F_JI_THRESHOLD``; finite, 0 <= t < 1).
         Returns a :class:`Result`; its host arrays stay valid as long as they are referenced
         (rgc_detach_host hands them over when the context moves on)."""
         bi, keep, flags = self._batch_in(n_mg, k, box_size, box_off, id_base, x, y, score, flags,
-                                         dev_meta)
+                                         dev_meta, ji_threshold)
         self._retire()
         bo = BatchOut()
         _check(lib.rgc_run(self._p, C.byref(bi), C.byref(bo)))
@@ -341,7 +364,7 @@ class Context:
         return self._result(bo, n_mg, k, flags)
 
     def submit(self, n_mg, k, box_size, box_off, id_base, x, y, score, flags=F_HOST_OUTPUTS,
-               dev_meta=None):
+               dev_meta=None, ji_threshold=None):
         """``run`` without waiting (rgc_submit): the batch is enqueued on the context's stream
         and :meth:`wait` returns its :class:`Result`.  One submission in flight per context;
         two contexts overlap the host side of batch i+1 with the device work of batch i, and on
@@ -349,7 +372,7 @@ class Context:
         general path (large micrographs) runs on the context's worker thread until ``wait``.
         The arrays passed in must stay alive until ``wait`` (kept here)."""
         bi, keep, flags = self._batch_in(n_mg, k, box_size, box_off, id_base, x, y, score, flags,
-                                         dev_meta)
+                                         dev_meta, ji_threshold)
         self._retire()
         _check(lib.rgc_submit(self._p, C.byref(bi)))
         self._pending = (keep, n_mg, k, flags)
@@ -364,7 +387,8 @@ class Context:
         del keep
         return self._result(bo, n_mg, k, flags, self)
 
-    def _batch_in(self, n_mg, k, box_size, box_off, id_base, x, y, score, flags, dev_meta):
+    def _batch_in(self, n_mg, k, box_size, box_off, id_base, x, y, score, flags, dev_meta,
+                  ji_threshold=None):
         # (kept lean: this runs once per batch inside the bench's timed region)
         if not (type(box_off) is np.ndarray and box_off.dtype == np.int64
                 and box_off.flags.c_contiguous):
@@ -388,16 +412,22 @@ class Context:
             dbo, did = int(dev_meta[0]), int(dev_meta[1])
         bi = BatchIn(n_mg, k, int(box_size), flags, box_off.ctypes.data, id_base.ctypes.data,
                      px, py, ps, dbo, did)
+        if ji_threshold is not None:   # (the library validates it: RGCError before any launch)
+            flags |= F_JI_THRESHOLD
+            bi.flags = flags
+            bi.ji_threshold = float(ji_threshold)
         return bi, keep, flags
 
     def consensus(self, n_mg, k, box_size, box_off, id_base, x, y, score, flags=0,
-                  dev_meta=None, node_limit=0, num_particles=None, timing=False):
+                  dev_meta=None, node_limit=0, num_particles=None, timing=False,
+                  ji_threshold=None):
         """get_cliques + run_ilp in one device pass (rgc_consensus, ABI 10): ``run``'s
         arguments, then the solver's ``node_limit`` and run_ilp's ``num_particles`` (None:
         all).  The per-clique arrays stay in HBM unless ``flags`` has ``F_HOST_OUTPUTS``.
+        ``ji_threshold`` as for ``run``.
         Returns a :class:`ConsensusResult` (plain copies of the pick arrays)."""
         bi, keep, flags = self._batch_in(n_mg, k, box_size, box_off, id_base, x, y, score, flags,
-                                         dev_meta)
+                                         dev_meta, ji_threshold)
         self._retire()
         opts = ConsensusOpts(int(node_limit), -1 if num_particles is None else int(num_particles),
                              F_TIMING if timing else 0)
@@ -429,7 +459,7 @@ class Context:
                 _copy(po.pcol, n, np.int32))
 
     def last_edges(self):
-        """Test hook: (u, v, ji) copies of the JI > 0.3 edges of the last run with F_EDGES
+        """Test hook: (u, v, ji) copies of the JI > threshold edges of the last run with F_EDGES
         (batch box indices; order unspecified)."""
         u, v, j = _i32p(), _i32p(), _f64p()
         n = _check(lib.rgc_last_edges(self._p, C.byref(u), C.byref(v), C.byref(j)))

@@ -60,6 +60,7 @@ def add_arguments(parser):
                         help="filter for the number of expected particles (int)")
     parser.add_argument("--get_cc", action="store_true",
                         help="filters cliques for those in the largest Connected Component (CC)")
+    gc.add_ji_threshold(parser)
     parser.add_argument("--node_limit", type=int, default=0,
                         help="branch-and-bound nodes per conflict component (0: the library "
                              "default), as for run_ilp")
@@ -74,6 +75,7 @@ def add_arguments(parser):
 
 def main(args):
     assert os.path.exists(args.in_dir), "Error - input directory does not exist"
+    gc.ji_threshold_of(args)   # (ValueError before a context exists or anything is deleted)
     world, rank, local = gc._dist_env()
     if world > 1:
         raise _lib.RGCError(
@@ -153,7 +155,8 @@ class _Run(gc._Run):
             r = self.ctx.consensus(part.n_mg, part.k, part.box_size, part.box_off, part.id_base,
                                    part.x, part.y, part.score, flags,
                                    node_limit=getattr(self.args, "node_limit", 0) or 0,
-                                   num_particles=self.args.num_particles)
+                                   num_particles=self.args.num_particles,
+                                   ji_threshold=self.ji)
             self.stats["h2d_bytes"] += r.h2d_bytes
             self.stats["d2h_bytes"] += r.d2h_bytes
             ch.res = _Res(r) if ch.res is None else ch.res.append(_Res(r))

@@ -7,8 +7,10 @@ an empty ``<base>.box`` for skipped micrographs) and the same exception classes 
 micrograph when the reference would crash.  The work between parsing and writing runs as
 batched HIP kernels (``librepic_gc.so``); there is no CPU fallback.
 
-Extra options (do not change outputs): ``--batch_boxes`` (boxes per device batch),
-``--threads`` (host parser threads), ``--device``.
+Extra options that do not change outputs: ``--batch_boxes`` (boxes per device batch),
+``--threads`` (host parser threads), ``--device``.  ``--ji_threshold T`` sets the Jaccard
+threshold above which two picks are joined (get_jaccard's ``threshold``, which the reference
+fixes at 0.3 at its call site, get_cliques.py:138); the default is the reference's.
 """
 from __future__ import annotations
 
@@ -47,6 +49,7 @@ def add_arguments(parser):
                         help="set output of cliques to be members sorted by picker name")
     parser.add_argument("--get_cc", action="store_true",
                         help="filters cliques for those in the largest Connected Component (CC)")
+    add_ji_threshold(parser)
     parser.add_argument("--batch_boxes", type=int, default=1 << 25,
                         help="max boxes per device batch (does not change outputs)")
     parser.add_argument("--threads", type=int, default=None,
@@ -56,6 +59,28 @@ def add_arguments(parser):
     # tests only: JSON {picker: [names in readdir order]} replayed instead of os.listdir, so
     # global box ids (and the consensus tie-breaks) match a recorded reference run
     parser.add_argument("--listing", type=_load_listing, default=None, help=argparse.SUPPRESS)
+
+
+def add_ji_threshold(parser):
+    parser.add_argument("--ji_threshold", type=_ji_type, default=_lib.JI_DEFAULT, metavar="T",
+                        help="join two picks of different pickers when their Jaccard index "
+                             "exceeds T (float, 0 <= T < 1; default: the reference's 0.3)")
+
+
+def _ji_type(text):
+    try:
+        return _lib.check_ji_threshold(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def ji_threshold_of(args):
+    """The run's ``ji_threshold`` for ``Context.run``: None for the reference's 0.3 (the
+    library's default path, no flag), else the validated value.  Raises ValueError for a value
+    outside [0, 1); the commands call it before a device context exists or out_dir is touched."""
+    t = getattr(args, "ji_threshold", None)
+    t = _lib.JI_DEFAULT if t is None else _lib.check_ji_threshold(t)
+    return None if t == _lib.JI_DEFAULT else t
 
 
 def _load_listing(path):
@@ -79,6 +104,7 @@ def main(args):
     """get_cliques.py:72-229 semantics; under torchrun (WORLD_SIZE > 1) every rank takes a
     contiguous shard of the micrographs on its own GPU."""
     assert os.path.exists(args.in_dir), "Error - input directory does not exist"
+    ji_threshold_of(args)   # (ValueError before a context exists or anything is deleted)
     world, rank, local = _dist_env()
     dev = args.device if getattr(args, "device", None) is not None else local
     # the HIP context is created before torch.distributed is imported (a child that
@@ -127,7 +153,9 @@ def _main(args, ctx, world, rank, run_cls=None, make_writer=None):
         if not dist.is_initialized():
             dist.init_process_group(_dist_backend(world))
     assert os.path.exists(args.in_dir), "Error - input directory does not exist"
-    # checked before anything is deleted: the device kernels are compiled for k <= MAX_K
+    # checked before anything is deleted: the threshold, and the device kernels are compiled
+    # for k <= MAX_K
+    ji_threshold_of(args)
     k_pre = len(_methods_after_reset(args.in_dir, args.out_dir))
     if k_pre > _lib.MAX_K:
         raise _lib.RGCError(f"{k_pre} picker directories in {args.in_dir}: this build supports "
@@ -229,6 +257,7 @@ class _Run:
         self.stats = dict(parse_s=0.0, device_s=0.0, write_s=0.0, micrographs=0, edges=0,
                           cliques=0, chunks=0)
         self.chunk = max(1, int(getattr(args, "chunk_mg", None) or CHUNK_MG))
+        self.ji = ji_threshold_of(args)
 
     # -- stages
     def plan_chunks(self):
@@ -257,7 +286,7 @@ class _Run:
                                     getattr(self.args, "batch_boxes", 1 << 25)):
             part = b if (m0 == 0 and m1 == b.n_mg) else b.slice(m0, m1)
             r = _FlatResult(self.ctx, part, self.args.get_cc, self.args.multi_out,
-                            getattr(self.args, "no_fused", False))
+                            getattr(self.args, "no_fused", False), self.ji)
             ch.res = r if ch.res is None else ch.res.append(r, int(b.box_off[m0 * self.k]))
         self.stats["device_s"] += time.time() - t0
         ok = ch.res.status == _lib.OK
@@ -499,7 +528,7 @@ class _FlatResult:
 
     PER_MG = ("status", "cc_max", "cc_cnt", "n_vert", "n_edges_mg", "clique_base", "clique_cnt")
 
-    def __init__(self, ctx, batch, get_cc, multi_out, no_fused=False):
+    def __init__(self, ctx, batch, get_cc, multi_out, no_fused=False, ji_threshold=None):
         flags = _lib.F_HOST_OUTPUTS
         if no_fused:
             flags |= _lib.F_NO_FUSED
@@ -508,7 +537,7 @@ class _FlatResult:
         if multi_out:
             flags |= _lib.F_MULTI_OUT
         r = ctx.run(batch.n_mg, batch.k, batch.box_size, batch.box_off, batch.id_base, batch.x,
-                    batch.y, batch.score, flags)
+                    batch.y, batch.score, flags, ji_threshold=ji_threshold)
         for f in self.PER_MG:
             setattr(self, f, np.array(getattr(r, f)))
         self.rows, self.w, self.conf = r.rows.copy(), r.w.copy(), r.conf.copy()

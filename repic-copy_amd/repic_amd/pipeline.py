@@ -67,8 +67,9 @@ class MgResult:
 
 
 def run_batch(ctx: _lib.Context, batch: Batch, get_cc=False, multi_out=False, timing=False,
-              members=False, no_fused=False):
-    """Run one packed batch on the device; returns list[MgResult] (batch-local box indices)."""
+              members=False, no_fused=False, ji_threshold=None):
+    """Run one packed batch on the device; returns list[MgResult] (batch-local box indices).
+    ``ji_threshold``: None for the reference's 0.3, as for ``Context.run``."""
     flags = _lib.F_HOST_OUTPUTS
     if members:
         flags |= _lib.F_MEMBERS
@@ -81,7 +82,7 @@ def run_batch(ctx: _lib.Context, batch: Batch, get_cc=False, multi_out=False, ti
     if timing:
         flags |= _lib.F_TIMING
     r = ctx.run(batch.n_mg, batch.k, batch.box_size, batch.box_off, batch.id_base, batch.x,
-                batch.y, batch.score, flags)
+                batch.y, batch.score, flags, ji_threshold=ji_threshold)
     out = []
     for m in range(batch.n_mg):
         q = MgResult()
