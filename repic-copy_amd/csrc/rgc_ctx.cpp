@@ -38,6 +38,9 @@ int ensure_dev(rgc_ctx* c, int id, size_t bytes, size_t keep) {
     HIPCHK(hipMemsetAsync(p, 0, cap, c->stream));
     c->tiles_epoch = scan_epoch_count();
   }
+  // the per-micrograph tie counts: zero wherever no fused workgroup has written since the last
+  // ties launch, so a new buffer starts all zero
+  if (id == D_TIECNT) HIPCHK(hipMemsetAsync(p, 0, cap, c->stream));
   return 0;
 }
 

@@ -93,9 +93,10 @@ struct FusedHdr {
   float inv_gy;
   int gx, gy, ncell, nkey;   // per-picker grid gx x gy; keys picker * ncell + cell; nkey = none
   // E: forward edges; P2's cursor (each wave-round reserves its block's lists on it)
-  int E, nodes, cc_cnt, cc_max, target, V, status;
+  int E, nodes, cc_cnt, cc_max, V, status;
   uint32_t ccur;    // P4 clique-queue cursor
-  int tief[2];      // P6: some clique of the chunk needs the order pass (by chunk parity)
+  uint32_t ntie;    // P6: cliques handed to k_fused_ties so far (the next one's segment slot)
+  int tief[2];      // P6: some clique of the chunk needs the second loop (by chunk parity)
   int qslot;        // QG (K = 4): the workgroup's HBM level-tree slot (-1: none, LDS queue)
   int64_t C, base;
 };
@@ -210,9 +211,10 @@ struct FCtx {
   uint16_t* cq_ord;  // P4 queue: ordinal of each queued clique within its root's DFS
   uint32_t* ccur;    // P4 queue cursor (LDS)
   int cq_cap;        // P4 queue capacity (cliques)
-  gptr<int32_t> tie_list;         // set-order ties for k_fused_ties
-  gptr<unsigned long long> tie_count;
-  int64_t tie_cap;
+  // cliques left to k_fused_ties: the micrograph's segment of the tie list (it starts at the
+  // micrograph's own clique base) and the LDS counter that hands out its slots
+  gptr<int32_t> tie_seg;
+  uint32_t* ntie;
 };
 
 __device__ __forceinline__ uint32_t lds_ld(uint32_t* p) {
@@ -435,12 +437,42 @@ __device__ __forceinline__ uint64_t ins_key(const FCtx<K>& c, int u) {
          ((uint64_t)(dmin - picker_begin<K>(c.pb, pd)) << 1);
 }
 
+// A clique this kernel does not decide (set-order micrographs: the f32 degrees are within the
+// margin, or --multi_out wants the node order) goes to k_fused_ties: the next slot of the
+// micrograph's tie segment, handed out by an LDS counter (the segment has a slot per clique of
+// the micrograph, so nothing is counted in HBM and nothing can overflow).  li = the members'
+// local (file-order) indices in picker order.
+template <int K>
+__device__ __forceinline__ void fused_tie_handoff(const FCtx<K>& c, int64_t j, const int (&li)[K]) {
+  const uint32_t t = atomicAdd(c.ntie, 1u);
+  gptr<int32_t> e = c.tie_seg + (int64_t)t * (4 + K);
+  e[0] = (int32_t)(uint32_t)(uint64_t)j;
+  e[1] = (int32_t)(uint32_t)((uint64_t)j >> 32);
+  e[2] = c.m;
+  e[3] = (c.flags & 2) ? 1 : 0;
+#pragma unroll
+  for (int i = 0; i < K; ++i) e[4 + i] = c.b0 + li[i];
+}
+
+// what fused_epilogue_main does with a clique it cannot decide: a set-order micrograph's is
+// handed off on the spot (every instance affords the entry store inside P6's main loop: none
+// loses an occupancy step or gains scratch for it, `make resources`); true = an insertion-order
+// graph's, flagged for the second loop
+template <int K>
+__device__ __forceinline__ bool fused_undecided(const FCtx<K>& c, int64_t j, const int (&li)[K]) {
+  if (c.set_order) {
+    fused_tie_handoff<K>(c, j, li);
+    return false;
+  }
+  return true;
+}
+
 // ILP epilogue of one buffered clique (thread per clique): reference get_cliques.py:169-202.
 // j = output index; mem = member positions in picker order.  Main pass: COO rows, weight,
-// confidence, members and the consensus when one member has the largest weighted degree;
-// returns true when the consensus needs the node-iteration order (a degree tie, or
-// --multi_out), which fused_epilogue_order computes in a second, rarely-taken pass (its
-// 64-bit hashing stays out of this pass's register budget).
+// confidence, members and the consensus when one member's weighted degree is the largest by
+// a clear margin.  Anything closer, and every clique under --multi_out, is decided exactly
+// elsewhere: k_fused_ties for set-order micrographs (fused_undecided), the second loop's
+// fused_epilogue_order for the tiny insertion-order graphs (returns true for those).
 // INTP (integer coordinates below 2^23, B <= 2896, f32 layout): every overlap B - |dx| and
 // product is an integer below 2^24, exact in f32, so the overlaps, their median network and the
 // f32 degree JIs (2 B^2 - I exact too) run on floats; the median overlaps are converted back
@@ -530,10 +562,10 @@ __device__ __forceinline__ bool fused_epilogue_main(const FCtx<K>& c, int64_t j,
 #pragma unroll
     for (int i = 0; i < K; ++i) c.members[j * K + i] = c.b0 + li[i];
   }
-  if (c.flags & 2) return true;
+  if (c.flags & 2) return fused_undecided<K>(c, j, li);
   // weighted degrees from f32 JIs: f32 operands (2^-24 each) and v_rcp_f32 (1 ulp) give
   // < 4e-7 per JI <= 1, < 5.5e-6 per sum of <= 7 terms with its f32 additions; a maximum
-  // clear by 3e-5 is the reference's, anything closer goes to the exact f64 pass (ties)
+  // clear by 3e-5 is the reference's, anything closer goes to an exact f64 pass
   float deg[K];
 #pragma unroll
   for (int i = 0; i < K; ++i) deg[i] = 0.0f;
@@ -560,7 +592,11 @@ __device__ __forceinline__ bool fused_epilogue_main(const FCtx<K>& c, int64_t j,
     arg = d > d1 ? i : arg;
     d1 = fmaxf(d1, d);
   }
-  if (!(d1 - d2 > 3e-5f)) return true;
+#ifndef RGC_ABL_NO_TIES
+  // (ablation build only, RGC_ABL_NO_TIES: every maximum counts as clear -- what the kernel
+  // would cost with no near-tie to hand off; its consensus is wrong by design)
+  if (!(d1 - d2 > 3e-5f)) return fused_undecided<K>(c, j, li);
+#endif
   int cons = li[0];
 #pragma unroll
   for (int i = 1; i < K; ++i) cons = (arg == i) ? li[i] : cons;
@@ -568,15 +604,15 @@ __device__ __forceinline__ bool fused_epilogue_main(const FCtx<K>& c, int64_t j,
   return false;
 }
 
-// second pass for the cliques fused_epilogue_main deferred: networkx node-iteration order
-// (CPython set order or graph insertion order), consensus among the tied maximal members,
-// and the --multi_out member order
+// second loop, insertion-order graphs (2k >= |G|, tiny): the exact f64 degrees, graph insertion
+// order (ins_key reads the LDS graph, so this stays in the kernel), consensus among the tied
+// maximal members, and the --multi_out member order
 template <int K, bool W>
 __device__ __forceinline__ void fused_epilogue_order(const FCtx<K>& c, int64_t j,
                                                      const int (&mem)[K]) {
   double ji[K][K], xs[K], ys[K];
   int li[K];
-  uint64_t ins[K] = {};
+  uint64_t ins[K];
 #pragma unroll
   for (int i = 0; i < K; ++i) {
     const double2 xy = ld_xy<W>(c.S, mem[i]);
@@ -588,35 +624,17 @@ __device__ __forceinline__ void fused_epilogue_order(const FCtx<K>& c, int64_t j
   for (int a = 0; a < K; ++a)
 #pragma unroll
     for (int b = a + 1; b < K; ++b) ji[a][b] = jaccard(xs[a], ys[a], xs[b], ys[b], c.B, c.two_b2);
-  if (!c.set_order) {
-    for (int i = 0; i < K; ++i) ins[i] = ins_key<K>(c, mem[i]);
-  }
+  for (int i = 0; i < K; ++i) ins[i] = ins_key<K>(c, mem[i]);
   uint32_t top;
   int arg = epi_degree_max<K>(ji, &top);
   const bool tie = (top & (top - 1)) != 0;
   const bool multi = (c.flags & 2) != 0;
   if (tie || multi) {
-    if (c.set_order) {
-      // CPython set order (64-bit tuple hashing and set probing): appended for k_fused_ties,
-      // which keeps that code out of this kernel's registers (ties: ~0.6 % of C2's cliques)
-      const unsigned long long t = atomicAdd((unsigned long long*)c.tie_count, 1ull);
-      if ((int64_t)t < c.tie_cap) {
-        gptr<int32_t> e = c.tie_list + (int64_t)t * (4 + K);
-        e[0] = (int32_t)(uint32_t)(uint64_t)j;
-        e[1] = (int32_t)(uint32_t)((uint64_t)j >> 32);
-        e[2] = c.m;
-        e[3] = (int32_t)(top | (tie ? 0x10000u : 0u) | (multi ? 0x20000u : 0u));
+    const uint32_t ord = node_order_ins<K>(ins);
+    if (tie) arg = epi_tie_arg<K>(top, ord);
+    if (multi) {
 #pragma unroll
-        for (int i = 0; i < K; ++i) e[4 + i] = c.b0 + li[i];
-      }
-      if (tie) return;   // consensus by k_fused_ties
-    } else {
-      const uint32_t ord = node_order_ins<K>(ins);
-      if (tie) arg = epi_tie_arg<K>(top, ord);
-      if (multi) {
-#pragma unroll
-        for (int i = 0; i < K; ++i) c.order[j * K + i] = (uint8_t)((ord >> (4 * i)) & 15);
-      }
+      for (int i = 0; i < K; ++i) c.order[j * K + i] = (uint8_t)((ord >> (4 * i)) & 15);
     }
   }
   int cons = li[0];
@@ -1303,7 +1321,9 @@ __device__ __forceinline__ void pairs_fill(const Stencil& st, const FShared& S, 
 // batch total (deferred ones are counted by the pass that finishes them)
 __device__ __forceinline__ void put_stats(const FusedArgs& A, int m, int status, int64_t edges,
                                           int nodes, int cc_cnt, int cc_max, int V, int64_t base,
-                                          int64_t C) {
+                                          int64_t C, int ties = 0) {
+  // entries this workgroup left in the micrograph's tie segment (0: its epilogue did not run)
+  A.tie_cnt[m] = ties;
   A.o.status[m] = status;
   A.o.cc_max[m] = cc_max;
   A.o.cc_cnt[m] = cc_cnt;
@@ -1432,8 +1452,7 @@ void k_fused(FusedArgs A) {
   c.rows = gdetach(A.rows); c.w = gdetach(A.w); c.conf = gdetach(A.conf);
   c.consensus = gdetach(A.consensus);
   c.members = gdetach(A.members); c.order = gdetach(A.order);
-  c.tie_list = gdetach(A.tie_list); c.tie_count = gdetach(A.cursor) + CUR_TIES;
-  c.tie_cap = sdetach(A.tie_cap);
+  c.ntie = &H.ntie;
   const gptr<const double> ax = gdetach(A.x);
   const gptr<const double> ay = gdetach(A.y);
   c.S = S;
@@ -1575,7 +1594,7 @@ void k_fused(FusedArgs A) {
       // -inf minimum: some coordinate is not an integer below 2^23 (P0), the host relaunches
       // the micrograph with the f64 layout
       H.status = (!W && mnx == -INFINITY) ? RGC_ST_DEFER_WIDE : 0;
-      H.C = 0; H.base = 0; H.V = 0; H.target = -1; H.ccur = 0; H.E = 0;
+      H.C = 0; H.base = 0; H.V = 0; H.ccur = 0; H.ntie = 0; H.E = 0;
       H.tief[0] = H.tief[1] = 0;
       H.qslot = 0;
     }
@@ -1866,8 +1885,9 @@ void k_fused(FusedArgs A) {
   }
 
   STOP_AFTER(2);
-  
-  // ---- P3: connected components: the unions ran in the P2 fill; compress, count sizes
+
+  // ---- P3: connected components: the unions ran edge-parallel behind P2's pass (one thread per
+  // edge); compress, count sizes
   STAMP(6);   // union (one thread per edge)
   // One loop compresses and takes the stats.  The flag and the parent are loaded together,
   // before the flag is tested (the list split P4 reads came from P2's count).  The size
@@ -1960,7 +1980,6 @@ void k_fused(FusedArgs A) {
 #pragma unroll
     for (int w = 0; w < FNW; ++w) best = H.redu[w] < best ? H.redu[w] : best;
     target = (int)(best & 0xFFFF);
-    if (tid == 0) H.target = target;
   }
 
   STOP_AFTER(3);
@@ -2204,10 +2223,13 @@ void k_fused(FusedArgs A) {
     }
 
     STAMP(11);  // score staging
-    // per chunk of queued cliques: main pass (thread per clique), then the order pass over
-    // the cliques it flagged (bit 15 of the slot's ordinal word; the slot's output index is
-    // kept in the low bits).  Micrographs whose cliques overflowed the queue re-walk the DFS
-    // per chunk of <= cq_cap cliques into the same buffer.
+    // per chunk of queued cliques: main pass (thread per clique).  A set-order micrograph
+    // (2 K < nodes: every real one) ends the chunk there: the main pass hands what it cannot
+    // decide to k_fused_ties itself.  An insertion-order graph takes a second loop over the
+    // cliques the main pass flagged (bit 15 of the slot's ordinal word; the slot's output index
+    // is kept in the low bits), behind a barrier and the chunk's H.tief: its f64 order pass.
+    // Micrographs whose cliques overflowed the queue re-walk the DFS per chunk of <= cq_cap
+    // cliques into the same buffer.
     // chunk bounds and the output base are wave-uniform and 32-bit (C < 2^31, checked at the
     // reservation): they live in SGPRs instead of spilled 64-bit VGPR pairs
     const int Cm = ufl((int)H.C);
@@ -2218,9 +2240,12 @@ void k_fused(FusedArgs A) {
     // the others are rebuilt there); DFS fallback: chunks of <= cap cliques re-walked into cbuf
     const int nit = bfs_ok ? nch : (Cm + cap - 1) / cap;
     BfsOut<K> cur = bo;
+    c.tie_seg = gdetach(A.tie_list) + obase * (4 + K);   // (obase + C <= cap = tie_cap)
+    const bool second = !c.set_order;   // (workgroup-uniform)
     for (int ci = 0; ci < nit; ++ci) {
       int c0, c1;
-      if (tid == 0) H.tief[(ci + 1) & 1] = 0;   // last read before the previous chunk's end
+      // (last read before the previous chunk's end)
+      if (second && tid == 0) H.tief[(ci + 1) & 1] = 0;
       if (bfs_ok) {
         const int ch = ci == 0 ? nch - 1 : ci - 1;
         c0 = ufl((int)chtab[2 * ch + 1]);
@@ -2311,14 +2336,16 @@ void k_fused(FusedArgs A) {
           epi(sl, mem);
         }
       }
-      if (any) H.tief[ci & 1] = 1;
-      __syncthreads();
-      if (H.tief[ci & 1]) {
-        for (int sl = tid; sl < c1 - c0; sl += FWG) {
-          if (!order_flag(sl)) continue;
-          int mem[K];
-          const int64_t jo = clique_members(sl, mem);
-          fused_epilogue_order<K, W>(c, jo, mem);
+      if (second) {
+        if (any) H.tief[ci & 1] = 1;
+        __syncthreads();
+        if (H.tief[ci & 1]) {
+          for (int sl = tid; sl < c1 - c0; sl += FWG) {
+            if (!order_flag(sl)) continue;
+            int mem[K];
+            const int64_t jo = clique_members(sl, mem);
+            fused_epilogue_order<K, W>(c, jo, mem);
+          }
         }
       }
       __syncthreads();
@@ -2341,15 +2368,22 @@ void k_fused(FusedArgs A) {
     }
   }
   if (tid == 0)
-    put_stats(A, m, H.status, H.E, H.nodes, H.cc_cnt, H.cc_max, H.V, H.base, H.C);
+    put_stats(A, m, H.status, H.E, H.nodes, H.cc_cnt, H.cc_max, H.V, H.base, H.C, (int)H.ntie);
 }
 
-// Consensus on set-order ties and the --multi_out node order of the cliques the fused kernel
-// appended (fused_epilogue_order): networkx iterates set(sorted(clique)) (get_cliques.py:182-183
-// -> CPython set order of the (x, y, id) node keys, pyset.h), first tied member in that order.
-// Grid-stride over the entries [from, cursor[CUR_TIES]).
+// The cliques the fused launches before it left undecided (fused_tie_handoff): the exact f64
+// weighted degrees from the batch coordinates (the reference's JIs, get_cliques.py:182-183),
+// the consensus where one member's is the largest, else the first tied member in networkx's
+// node order = CPython set order of the (x, y, id) node keys (set(sorted(clique)), pyset.h);
+// the --multi_out node order.  Micrograph m's entries are the first tie_cnt[m] slots of the
+// tie list from its clique base.  A workgroup takes G consecutive micrographs (one thread each:
+// count and base), scans the counts and spreads the (micrograph, entry) pairs over its 256
+// threads, so C2's ~3 entries in each of 10k micrographs do not serialise on one lane and C4's
+// uneven dozens per micrograph even out; G shrinks with the batch until every workgroup of the
+// launch has work.  Each consumed count is cleared: the launch behind a later fused pass, or
+// the context's next run, sees only new entries.
 template <int K>
-__global__ __launch_bounds__(256) void k_fused_ties(FusedArgs A, int64_t from) {
+__global__ __launch_bounds__(256) void k_fused_ties(FusedArgs A) {
   if (A.esum_n > 0 && blockIdx.x < 16) {
     // edges of the finished micrographs into cursor[1]: 16 workgroups, one atomic each
     __shared__ int64_t red[4];
@@ -2361,31 +2395,78 @@ __global__ __launch_bounds__(256) void k_fused_ties(FusedArgs A, int64_t from) {
     e = block_sum64<256>(e, red);
     if (threadIdx.x == 0 && e) atomicAdd(A.cursor + 1, (unsigned long long)e);
   }
-  const int64_t n = min((int64_t)__hip_atomic_load(A.cursor + CUR_TIES, __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT), A.tie_cap);
-  for (int64_t t = from + (int64_t)blockIdx.x * 256 + threadIdx.x; t < n;
-       t += (int64_t)gridDim.x * 256) {
-    const int32_t* e = A.tie_list + t * (4 + K);
-    const int64_t j = (int64_t)(((uint64_t)(uint32_t)e[1] << 32) | (uint32_t)e[0]);
-    const int m = e[2];
-    const uint32_t fl = (uint32_t)e[3];
-    const int64_t idb = A.id_base[m] - (int64_t)A.box_off[m * K];
-    int mem[K];
-    double xs[K], ys[K];
-    int64_t ids[K];
-    const uint64_t ins[K] = {};
+  {
+    __shared__ int s_inc[256];
+    __shared__ int64_t s_base[256];
+    __shared__ int s_wave[4];
+    const int tid = threadIdx.x;
+    const int G = min(max((A.tie_n + (int)gridDim.x - 1) / (int)gridDim.x, 1), 256);
+    const int ngrp = (A.tie_n + G - 1) / G;
+    for (int g = (int)blockIdx.x; g < ngrp; g += (int)gridDim.x) {
+      const int m = g * G + tid;
+      int cnt = 0;
+      int64_t base = 0;
+      if (tid < G && m < A.tie_n) {
+        cnt = A.tie_cnt[m];
+        if (cnt > 0) {
+          base = A.o.clique_base[m];
+          A.tie_cnt[m] = 0;
+          // (a segment lies inside the list by construction; never read past it)
+          if (cnt > A.o.clique_cnt[m] || base < 0 || base + cnt > A.tie_cap) cnt = 0;
+        }
+      }
+      int inc = wave_incl_scan(cnt, [](int a, int b) { return a + b; });
+      __syncthreads();   // the previous trip's reads
+      if ((tid & 63) == 63) s_wave[tid >> 6] = inc;
+      __syncthreads();
+      for (int w = 0; w < (tid >> 6); ++w) inc += s_wave[w];
+      s_inc[tid] = inc;
+      s_base[tid] = base - (inc - cnt);   // entry index of pair p: s_base + p
+      __syncthreads();
+      const int total = s_inc[255];
+      for (int p = tid; p < total; p += 256) {
+        // the pair's micrograph: the first thread whose inclusive count exceeds p
+        int lo = 0;
 #pragma unroll
-    for (int i = 0; i < K; ++i) {
-      mem[i] = e[4 + i];
-      xs[i] = A.x[mem[i]];
-      ys[i] = A.y[mem[i]];
-      ids[i] = idb + mem[i];
-    }
-    const uint32_t ord = node_order<K>(mem, xs, ys, ids, true, ins);
-    if (fl & 0x10000u) A.consensus[j] = mem[epi_tie_arg<K>(fl & 0xFFFFu, ord)];
-    if (fl & 0x20000u) {
+        for (int st = 128; st > 0; st >>= 1)
+          if (s_inc[lo + st - 1] <= p) lo += st;
+        const int32_t* e = A.tie_list + (s_base[lo] + p) * (4 + K);
+        const int64_t j = (int64_t)(((uint64_t)(uint32_t)e[1] << 32) | (uint32_t)e[0]);
+        const int me = e[2];
+        const bool multi = (e[3] & 1) != 0;
+        const int64_t idb = A.id_base[me] - (int64_t)A.box_off[me * K];
+        int mem[K];
+        double xs[K], ys[K], ji[K][K];
+        int64_t ids[K];
+        const uint64_t ins[K] = {};
 #pragma unroll
-      for (int i = 0; i < K; ++i) A.order[j * K + i] = (uint8_t)((ord >> (4 * i)) & 15);
+        for (int i = 0; i < K; ++i) {
+          mem[i] = e[4 + i];
+          xs[i] = A.x[mem[i]];
+          ys[i] = A.y[mem[i]];
+          ids[i] = idb + mem[i];
+        }
+#pragma unroll
+        for (int a = 0; a < K; ++a)
+#pragma unroll
+          for (int b = a + 1; b < K; ++b)
+            ji[a][b] = jaccard(xs[a], ys[a], xs[b], ys[b], A.B, A.two_b2);
+        uint32_t top;
+        int arg = epi_degree_max<K>(ji, &top);
+        const bool tie = (top & (top - 1)) != 0;
+        if (tie || multi) {
+          const uint32_t ord = node_order<K>(mem, xs, ys, ids, true, ins);
+          if (tie) arg = epi_tie_arg<K>(top, ord);
+          if (multi) {
+#pragma unroll
+            for (int i = 0; i < K; ++i) A.order[j * K + i] = (uint8_t)((ord >> (4 * i)) & 15);
+          }
+        }
+        int cons = mem[0];
+#pragma unroll
+        for (int i = 1; i < K; ++i) cons = (arg == i) ? mem[i] : cons;
+        A.consensus[j] = cons;
+      }
     }
   }
   if (A.host_stats) {
@@ -2399,13 +2480,23 @@ __global__ __launch_bounds__(256) void k_fused_ties(FusedArgs A, int64_t from) {
   }
 }
 
-int launch_fused_ties(hipStream_t stream, const FusedArgs& A, int64_t from) {
-  if (!A.tie_list || A.tie_cap <= from) return 0;
-  // (256 workgroups: 32 were 6 % slower on C4, whose steps hold thousands of tie entries)
-  const dim3 g(256), b(256);
+int launch_fused_ties(hipStream_t stream, const FusedArgs& A) {
+  if (!A.tie_list || !A.tie_cnt || A.tie_cap <= 0) return 0;
+  // A workgroup walks its pairs 256 at a time, and a trip costs about what the whole kernel
+  // did with one entry per thread (tuple hashing: ~11 us at k = 5), so k >= 4, whose
+  // micrographs leave a dozen to dozens of entries each, launches as wide as 1024 workgroups
+  // (four micrographs each while the batch allows); k <= 3 (C2: ~3 entries per micrograph)
+  // stays at 256, where the wider launch only cost ("Near-ties by clique
+  // slot").  RGC_TIES_GRID: a fixed grid, timing experiments only
+#ifdef RGC_TIES_GRID
+  const int nb = RGC_TIES_GRID;
+#else
+  const int nb = A.k <= 3 ? 256 : std::min(std::max((A.tie_n + 3) / 4, 256), 1024);
+#endif
+  const dim3 g(nb), b(256);
   switch (A.k) {
 #define RGC_TIES_CASE(KK) \
-  case KK: hipLaunchKernelGGL((k_fused_ties<KK>), g, b, 0, stream, A, from); break;
+  case KK: hipLaunchKernelGGL((k_fused_ties<KK>), g, b, 0, stream, A); break;
     RGC_TIES_CASE(2) RGC_TIES_CASE(3) RGC_TIES_CASE(4) RGC_TIES_CASE(5) RGC_TIES_CASE(6)
     RGC_TIES_CASE(7) RGC_TIES_CASE(8)
 #undef RGC_TIES_CASE

@@ -43,8 +43,8 @@ enum DevBufId {
   D_LCNT, D_LOFF, D_LROOT0, D_LROOT1, D_LM0, D_LM1, D_LP0, D_LP1, D_PK,
   // HBM level-tree slots of the 1024-thread fused launches (K >= 4)
   D_QG, D_QGSLOT,
-  // set-order tie entries of the fused launches (k_fused_ties)
-  D_TIES,
+  // tie entries of the fused launches and their per-micrograph counts (k_fused_ties)
+  D_TIES, D_TIECNT,
   // RGC_F_EDGES test hook
   D_EU, D_EV, D_EJIOUT,
   // score_detections raster
@@ -74,9 +74,7 @@ struct Buf {
 };
 
 // device cursors after the per-micrograph block: [0] cliques [1] edges of finished
-// micrographs [2] edge-dump reservation (RGC_F_EDGES) [4] deferrals [5] f64-pass micrographs;
-// [CUR_TIES] ties, on its own 64-B line (its per-wave atomics would queue behind the
-// reservations on cursor[0]'s line)
+// micrographs [2] edge-dump reservation (RGC_F_EDGES) [4] deferrals [5] f64-pass micrographs
 constexpr size_t CUR_BYTES = 128;
 
 struct rgc_ctx {

@@ -95,9 +95,6 @@ struct MgStat {
   int n_nodes, cc_cnt, cc_max, status, target, n_vert;
 };
 
-// cursor block word of the set-order tie count (a separate 64-B line from cursor[0])
-constexpr int CUR_TIES = 8;
-
 // internal per-micrograph status codes (0..2 are the public RGC_* codes)
 constexpr int RGC_ST_NO_EDGES = 1;
 constexpr int RGC_ST_NO_CLIQUES = 2;
@@ -158,7 +155,7 @@ struct FusedArgs {
   // [0] clique-range reservation, [1] edges of finished mgs (summed by k_fused_ties over the
   // first esum_n micrographs' stats; no per-workgroup atomic: 10k workgroups adding to one
   // word cost ~8 % of C2's kernel), [2] edge dump, [4] deferrals, [5] f32-pass micrographs
-  // deferred to the f64 layout (DEFER_WIDE), [CUR_TIES] ties
+  // deferred to the f64 layout (DEFER_WIDE)
   unsigned long long* cursor;
   // cursors of the context's other run slot: zeroed by block 0 for the next run (no memset
   // packet between runs)
@@ -182,11 +179,17 @@ struct FusedArgs {
   char* qg_base;
   uint32_t* qg_slots;
   int qg_nslots, qg_bytes;
-  // cliques whose consensus / --multi_out order needs CPython set order (degree ties with
-  // 2k < |G|): entries of 4 + k int32 (j lo, j hi, micrograph, top | tie << 16 | multi << 17,
-  // k batch box indices) for k_fused_ties, counted on cursor[CUR_TIES]; tie_cap entries
+  // cliques of set-order micrographs (2k < |G|) whose consensus the fused kernel's f32 degrees
+  // cannot decide, and every clique under --multi_out: entries of 4 + k int32 (j lo, j hi,
+  // micrograph, multi bit, k batch box indices) for k_fused_ties.  Micrograph m's entries are
+  // tie_list[clique_base[m] .. + tie_cnt[m]), tie_cnt[m] <= clique_cnt[m]: one slot per output
+  // clique (tie_cap = cap), so the segments are disjoint and need no counter.  Every fused
+  // workgroup writes its tie_cnt[m] (0 when its epilogue did not run); k_fused_ties clears
+  // the counts it consumed, so tie_cnt is all zero between a ties launch and the next fused one.
   int32_t* tie_list;
   int64_t tie_cap;
+  int32_t* tie_cnt;
+  int tie_n;    // k_fused_ties: micrographs of the batch (tie_cnt entries it walks)
   int esum_n;   // k_fused_ties: micrographs whose finished edges it sums into cursor[1]
   // device-side f64 pass (rgc_submit): the f32 pass appends its DEFER_WIDE micrographs to
   // wide_list (count cursor[5]) instead of counting them as deferrals; the f64 launch that
@@ -207,8 +210,8 @@ int fused_vgprs(int k, bool wide, int nt);
 bool fused_nt_ok(int k, int nt);
 int launch_fused(hipStream_t stream, int n_blocks, int lds_bytes, const FusedArgs& A, bool wide,
                  int nt);
-// the tie entries [from, cursor[CUR_TIES]) of the fused launches before it (CPython set order)
-int launch_fused_ties(hipStream_t stream, const FusedArgs& A, int64_t from);
+// the tie entries of the fused launches before it (exact f64 degrees, CPython set order)
+int launch_fused_ties(hipStream_t stream, const FusedArgs& A);
 void launch_gather(hipStream_t stream, int n_sub, int k, const int32_t* sub_mg,
                    const int32_t* box_off, const int32_t* sub_box_off, const double* x,
                    const double* y, const double* s, double* ox, double* oy, double* os,

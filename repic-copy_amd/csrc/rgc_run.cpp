@@ -154,6 +154,7 @@ struct FusedIo {
 static int fused_io(rgc_ctx* c, int n_mg, size_t cur_off, FusedIo* io) {
   TRY(ensure_host(c, H_MGOUT, cur_off + 2 * CUR_BYTES));
   TRY(ensure_dev(c, D_MGOUT, cur_off + 2 * CUR_BYTES));
+  TRY(ensure_dev(c, D_TIECNT, (size_t)n_mg * 4));   // (zeroed when it is allocated)
   char* d = D<char>(c, D_MGOUT);
   if (c->slots_at != d || c->slots_off != cur_off) {   // new buffer or layout: zero both slots
     HIPCHK(hipMemsetAsync(d + cur_off, 0, 2 * CUR_BYTES, c->stream));
@@ -287,6 +288,8 @@ static FusedArgs fused_args(rgc_ctx* c, const BatchShape& b, const rgc_batch_in*
   A.order = b.multi ? D<uint8_t>(c, D_ORDER) : nullptr;
   A.tie_list = D<int32_t>(c, D_TIES);
   A.tie_cap = c->cap_cliques;
+  A.tie_cnt = D<int32_t>(c, D_TIECNT);
+  A.tie_n = b.n_mg;
   return A;
 }
 
@@ -459,7 +462,6 @@ int Run::fused_attempt(int attempt, std::vector<int32_t>& todo, bool* overflow) 
   A.ev = b.want_edges ? D<int32_t>(c, D_EV) : nullptr;
   A.eji = b.want_edges ? D<double>(c, D_EJIOUT) : nullptr;
   A.ecap_out = c->cap_edges;
-  int64_t ties_done = 0;   // entries of earlier passes already resolved
 #ifdef RGC_STAMPS
   TRY(ensure_dev(c, D_STAMPS, 3 * (size_t)n_mg * rgc::STAMP_SLOTS * 8));
   HIPCHK(hipMemsetAsync(D<void>(c, D_STAMPS), 0, 3 * (size_t)n_mg * rgc::STAMP_SLOTS * 8, s));
@@ -507,14 +509,13 @@ int Run::fused_attempt(int attempt, std::vector<int32_t>& todo, bool* overflow) 
       TRY(launch_plan(c, A, plans.get(pass, keys[q]), single ? n_mg : (int)lists[q].size()));
     }
     TRY(mark(c, "k_fused_ties"));
-    if (launch_fused_ties(s, A, ties_done) != 0) return fail("tie kernel launch failed");
+    if (launch_fused_ties(s, A) != 0) return fail("tie kernel launch failed");
     TRY(mark(c, "d2h_stats"));
     HIPCHK(hipMemcpyAsync(H<void>(c, H_MGOUT), D<void>(c, D_MGOUT), cur_off + 2 * CUR_BYTES,
                           hipMemcpyDeviceToHost, s));
     TRY(record_tail(c));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
-    ties_done = std::min<int64_t>((int64_t)io.h_cur[rgc::CUR_TIES], A.tie_cap);
     ml_off += (int)by.size();
     todo.clear();
     for (int32_t i = 0, n = single ? n_mg : (int32_t)by.size(); i < n; ++i) {
@@ -839,7 +840,7 @@ static int submit_fast(rgc_ctx* c, const rgc_batch_in* in) {
     A.stats_bytes = (int64_t)co;
   }
   TRY(mark(c, "k_fused_ties"));
-  if (launch_fused_ties(s, A, 0) != 0) return fail("tie kernel launch failed (submit)");
+  if (launch_fused_ties(s, A) != 0) return fail("tie kernel launch failed (submit)");
   c->pend_slot = io.slot;
   c->cur_slot = 1 - c->cur_slot;   // the launch zeroes the other slot: the next run's
   TRY(record_tail(c));
