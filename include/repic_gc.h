@@ -150,7 +150,7 @@ int rgc_run(rgc_ctx* ctx, const rgc_batch_in* in, rgc_batch_out* out);
  * host once per clique level, so a second context on its own stream keeps the device busy
  * meanwhile), and one whose micrographs need a second pass re-runs that path inside rgc_wait.
  * Outputs stay valid until the next submit/run on the same context.  While a submitted
- * run awaits rgc_wait, rgc_submit, rgc_run, rgc_score_pairs and rgc_ilp_solve on the same
+ * run awaits rgc_wait, rgc_submit, rgc_run, rgc_score_pairs, rgc_score_sweep and rgc_ilp_solve on the same
  * context fail (negative return, rgc_last_error says why). */
 int rgc_submit(rgc_ctx* ctx, const rgc_batch_in* in);
 int rgc_wait(rgc_ctx* ctx, rgc_batch_out* out);
@@ -190,6 +190,26 @@ typedef struct rgc_score_in {
   uint32_t flags;          /* RGC_F_TIMING */
 } rgc_score_in;
 int rgc_score_pairs(rgc_ctx* ctx, const rgc_score_in* in, int64_t* counts);
+
+/* Confidence-threshold sweep of score_detections: what rgc_score_pairs returns for the picks
+ * kept at each of n_thr ascending thresholds (a pick is kept at t iff not conf < t,
+ * score_detections.py:34-36), from one launch that paints every box once (k_score_sweep).  The
+ * caller orders each pair's picks so that the ones kept at threshold j are a prefix and gives
+ * the prefix lengths.  counts[p][j] = sum(gt_arr), sum(pckr_arr at threshold j),
+ * sum(gt_arr * pckr_arr at threshold j).  RGC_F_TIMING (pairs.flags) records "k_score_sweep".
+ * Refused before any launch, the context staying usable: n_thr outside 1..RGC_SCORE_MAX_THR, a
+ * keep that is negative, larger than the pair's pick count or increasing in j, a submitted run
+ * awaiting rgc_wait, and whatever rgc_score_pairs refuses.
+ * An additive symbol: no struct changes layout and RGC_ABI_VERSION stays 11; a caller finds out
+ * whether the library has it by looking the symbol up. */
+#define RGC_SCORE_MAX_THR 1024
+typedef struct rgc_score_sweep_in {
+  rgc_score_in pairs;      /* as for rgc_score_pairs; each pair's picks ordered as above */
+  int32_t n_thr;           /* T, 1..RGC_SCORE_MAX_THR */
+  const int64_t* keep;     /* [n_pairs * T] picks of pair p kept at threshold j:
+                              boxes[pk_off[p], pk_off[p] + keep[p*T+j]) */
+} rgc_score_sweep_in;
+int rgc_score_sweep(rgc_ctx* ctx, const rgc_score_sweep_in* in, int64_t* counts /* [n_pairs][T][3] */);
 
 /* run_ilp (repic/commands/run_ilp.py:50-63): maximise w.x over binary x subject to A x <= 1,
  * exactly, for a batch of micrographs at once (rows are global box ids: micrographs never

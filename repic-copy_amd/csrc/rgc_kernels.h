@@ -357,6 +357,11 @@ struct ScoreArgs {
 };
 int score_tile_words();
 void launch_score_raster(hipStream_t stream, int n_tiles, const ScoreArgs& A);
+// threshold sweep (k_score_sweep): pair p's picks kept at threshold j are the first keep[p*T+j]
+// (non-increasing in j); counts is [n_pairs][T][3], zeroed: [p][0][0] receives sum(gt) and
+// [p][j][1..2] the pick pixels (and those under gt) that first appear at threshold j
+void launch_score_sweep(hipStream_t stream, int n_tiles, const ScoreArgs& A, int T,
+                        const int64_t* keep);
 
 // run_ilp exact set packing (rgc_ilp.hip)
 struct IlpArgs {

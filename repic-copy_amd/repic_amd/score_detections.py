@@ -8,6 +8,11 @@ same ``particle_set_comp.tsv``.  The (H x W) int16 masks the reference paints
 (score_detections.py:28-41) are never materialised: ``librepic_gc.so``'s ``rgc_score_pairs``
 paints 1-bit tiles in LDS and returns three pixel counts per pair (rgc_score.hip), many
 micrograph pairs per launch (``score_pairs``).  No CPU fallback: the library must load.
+
+Beyond the reference: ``score_sweep`` / ``sweep_counts`` give what ``score_pairs`` gives at each
+of a list of confidence thresholds from one launch that paints every box once
+(``rgc_score_sweep``), and ``--sweep T [T ...]`` writes those curves per file
+(``particle_set_sweep.tsv``) and pooled over all files (``particle_set_sweep_pooled.tsv``).
 """
 from __future__ import annotations
 
@@ -35,6 +40,14 @@ class ScoreIn(C.Structure):
 
 _lib.lib.rgc_score_pairs.argtypes = [C.c_void_p, C.POINTER(ScoreIn), C.c_void_p]
 _lib.lib.rgc_score_pairs.restype = C.c_int
+
+
+class ScoreSweepIn(C.Structure):
+    _fields_ = [("pairs", ScoreIn), ("n_thr", C.c_int32), ("keep", C.c_void_p)]
+
+
+_lib.lib.rgc_score_sweep.argtypes = [C.c_void_p, C.POINTER(ScoreSweepIn), C.c_void_p]
+_lib.lib.rgc_score_sweep.restype = C.c_int
 
 
 def _py_round(v):
@@ -67,13 +80,15 @@ def _as_cols(boxes):
     return tuple(np.asarray(c) for c in cols[:4]) + (np.asarray(conf, dtype=np.float64),)
 
 
-def _mask_slices(x, y, w, h, H, W):
-    """Non-empty numpy slices [r0, r1) x [c0, c1) of ``arr[y:y+h, x:x+w] = 1``."""
+def _mask_slices(x, y, w, h, H, W, kept=False):
+    """Non-empty numpy slices [r0, r1) x [c0, c1) of ``arr[y:y+h, x:x+w] = 1``; with ``kept``
+    also the mask of the boxes that have one."""
     xi, yi, wi, hi = (_py_round(v) for v in (x, y, w, h))
     r0, r1 = _slice_bounds(yi, H), _slice_bounds(yi + hi, H)
     c0, c1 = _slice_bounds(xi, W), _slice_bounds(xi + wi, W)
     keep = (r0 < r1) & (c0 < c1)
-    return np.stack([r0[keep], r1[keep], c0[keep], c1[keep]], axis=1).astype(np.int32)
+    s = np.stack([r0[keep], r1[keep], c0[keep], c1[keep]], axis=1).astype(np.int32)
+    return (s, keep) if kept else s
 
 
 def _scores(counts, H, W):
@@ -104,13 +119,7 @@ def score_pairs(pairs, conf_thresh=None, mrc_w=None, mrc_h=None, ctx=None, timin
     for gt, pk in pairs:
         g = _as_cols(gt)
         p = _as_cols(pk)
-        # mrc_w / mrc_h default: round(max(x + w)) over every box, thresholded or not (:22-26)
-        W = mrc_w if mrc_w is not None else int(_py_round(np.max(np.concatenate(
-            [g[0] + g[2], p[0] + p[2]]))))
-        H = mrc_h if mrc_h is not None else int(_py_round(np.max(np.concatenate(
-            [g[1] + g[3], p[1] + p[3]]))))
-        if H < 0 or W < 0:
-            raise ValueError("negative dimensions are not allowed")
+        H, W = _pair_dims(g, p, mrc_w, mrc_h)
         if conf_thresh is not None:
             keep = ~(p[4] < conf_thresh)          # b.conf < conf_thresh -> skipped (:35-36)
             p = tuple(c[keep] for c in p)
@@ -118,8 +127,33 @@ def score_pairs(pairs, conf_thresh=None, mrc_w=None, mrc_h=None, ctx=None, timin
         pks.append(_mask_slices(*p[:4], H, W))
         Hs.append(H)
         Ws.append(W)
-    # every pair's ground-truth boxes, then every pair's picks
     npairs = len(Hs)
+    si, H, W, hold = _score_in(gts, pks, Hs, Ws, timing)
+    counts = np.zeros((npairs, 3), dtype=np.int64)
+    ctx._retire()   # a live Result of an earlier run keeps its host buffers
+    _lib._check(_lib.lib.rgc_score_pairs(ctx._p, C.byref(si), counts.ctypes.data))
+    del hold
+    out = [_scores(counts[i], int(H[i]), int(W[i])) for i in range(npairs)]
+    if timing:
+        return out, dict(ctx.kernel_times())
+    return out
+
+
+def _pair_dims(g, p, mrc_w, mrc_h):
+    """(H, W) of a pair's masks from its (x, y, w, h, conf) columns."""
+    # mrc_w / mrc_h default: round(max(x + w)) over every box, thresholded or not (:22-26)
+    W = mrc_w if mrc_w is not None else int(_py_round(np.max(np.concatenate(
+        [g[0] + g[2], p[0] + p[2]]))))
+    H = mrc_h if mrc_h is not None else int(_py_round(np.max(np.concatenate(
+        [g[1] + g[3], p[1] + p[3]]))))
+    if H < 0 or W < 0:
+        raise ValueError("negative dimensions are not allowed")
+    return H, W
+
+
+def _score_in(gts, pks, Hs, Ws, timing):
+    """rgc_score_in of per-pair slice arrays: every pair's ground-truth boxes, then every
+    pair's picks -> (ScoreIn, H, W, the arrays it points into)."""
     z = np.zeros((0, 4), np.int32)
     boxes = np.ascontiguousarray(np.concatenate(gts + pks + [z]), dtype=np.int32)
     ng = np.cumsum([0] + [len(v) for v in gts]).astype(np.int64)
@@ -127,15 +161,114 @@ def score_pairs(pairs, conf_thresh=None, mrc_w=None, mrc_h=None, ctx=None, timin
     pk_arr = (ng[-1] + np.cumsum([0] + [len(v) for v in pks])).astype(np.int64)
     H = np.asarray(Hs, dtype=np.int64)
     W = np.asarray(Ws, dtype=np.int64)
-    counts = np.zeros((npairs, 3), dtype=np.int64)
-    si = ScoreIn(npairs, H.ctypes.data, W.ctypes.data, gt_arr.ctypes.data, pk_arr.ctypes.data,
+    si = ScoreIn(len(Hs), H.ctypes.data, W.ctypes.data, gt_arr.ctypes.data, pk_arr.ctypes.data,
                  boxes.ctypes.data, _lib.F_TIMING if timing else 0)
+    return si, H, W, (boxes, gt_arr, pk_arr)
+
+
+# ------------------------------------------------------------------------- threshold sweep
+def _check_threshs(conf_threshs):
+    """The thresholds of a sweep as a float64 array: any non-NaN floats, at least one."""
+    ts = np.asarray(list(conf_threshs), dtype=np.float64).reshape(-1)
+    if ts.size == 0:
+        raise ValueError("conf_threshs is empty: a sweep needs at least one threshold")
+    if np.isnan(ts).any():
+        raise ValueError("conf_threshs holds NaN: every pick would be kept at it, as at -inf")
+    return ts
+
+
+def _sweep_plan(conf, uniq):
+    """Order of a pair's picks for the sweep over the ascending unique thresholds ``uniq``.
+    A pick is kept at t iff not (conf < t) (score_detections.py:34-36), so its level, the number
+    of thresholds that keep it, is the count of t <= conf (all of them for a NaN confidence)
+    and it is kept at ``uniq[j]`` iff level > j.  -> (order, keep): ``order`` sorts the picks by
+    level descending (stable), ``keep[j]`` picks of that order are kept at ``uniq[j]``."""
+    conf = np.asarray(conf, dtype=np.float64)
+    level = np.searchsorted(uniq, conf, side="right")
+    level[np.isnan(conf)] = len(uniq)
+    order = np.argsort(-level, kind="stable")
+    below = np.cumsum(np.bincount(level, minlength=len(uniq) + 1))[:len(uniq)]   # level <= j
+    keep = (len(level) - below).astype(np.int64)
+    return order, keep
+
+
+def _sweep(pairs, conf_threshs, mrc_w=None, mrc_h=None, ctx=None, timing=False):
+    """-> (counts (n_pairs, T, 3) in the caller's threshold order, H, W, kernel times)."""
+    ts = _check_threshs(conf_threshs)
+    uniq, inv = np.unique(ts, return_inverse=True)
+    ctx = ctx or _ctx()
+    Hs, Ws, gts, pks, keeps = [], [], [], [], []
+    for gt, pk in pairs:
+        g = _as_cols(gt)
+        p = _as_cols(pk)
+        H, W = _pair_dims(g, p, mrc_w, mrc_h)
+        s, has = _mask_slices(*p[:4], H, W, kept=True)
+        order, keep = _sweep_plan(np.asarray(p[4], dtype=np.float64)[has], uniq)
+        gts.append(_mask_slices(*g[:4], H, W))
+        pks.append(s[order])
+        keeps.append(keep)
+        Hs.append(H)
+        Ws.append(W)
+    npairs, T = len(Hs), len(uniq)
+    si, H, W, hold = _score_in(gts, pks, Hs, Ws, timing)
+    keep = np.ascontiguousarray(np.concatenate(keeps + [np.zeros(0, np.int64)]), dtype=np.int64)
+    counts = np.zeros((npairs, T, 3), dtype=np.int64)
+    sw = ScoreSweepIn(si, T, keep.ctypes.data)
     ctx._retire()   # a live Result of an earlier run keeps its host buffers
-    _lib._check(_lib.lib.rgc_score_pairs(ctx._p, C.byref(si), counts.ctypes.data))
-    out = [_scores(counts[i], int(H[i]), int(W[i])) for i in range(npairs)]
-    if timing:
-        return out, dict(ctx.kernel_times())
-    return out
+    _lib._check(_lib.lib.rgc_score_sweep(ctx._p, C.byref(sw), counts.ctypes.data))
+    del hold
+    return counts[:, inv.reshape(-1), :], H, W, (dict(ctx.kernel_times()) if timing else None)
+
+
+def sweep_counts(pairs, conf_threshs, mrc_w=None, mrc_h=None, ctx=None, timing=False):
+    """The three pixel counts (sum(gt), sum(pckr), sum(gt * pckr)) of every pair at every
+    threshold of ``conf_threshs`` from one device call that paints each box once
+    (``rgc_score_sweep``): an (n_pairs, T, 3) int64 array in the order the thresholds were
+    given (any order, duplicates and +-inf allowed; NaN or an empty list: ValueError).  With
+    ``timing`` also the kernel ms."""
+    counts, _, _, ms = _sweep(pairs, conf_threshs, mrc_w, mrc_h, ctx, timing)
+    return (counts, ms) if timing else counts
+
+
+def score_sweep(pairs, conf_threshs, mrc_w=None, mrc_h=None, ctx=None, timing=False):
+    """``score_pairs`` at every threshold of ``conf_threshs`` in one device call:
+    ``score_sweep(pairs, ts)[i][j] == score_pairs(pairs, conf_thresh=ts[j])[i]``."""
+    counts, H, W, ms = _sweep(pairs, conf_threshs, mrc_w, mrc_h, ctx, timing)
+    out = [[_scores(c, int(H[i]), int(W[i])) for c in counts[i]] for i in range(len(H))]
+    return (out, ms) if timing else out
+
+
+def _sweep_rows(names, conf_threshs, counts, H, W):
+    """Rows of particle_set_sweep.tsv: grouped by file, thresholds in the order given."""
+    return [(m, repr(float(t))) + _scores(counts[i][j], int(H[i]), int(W[i]))
+            for i, m in enumerate(names) for j, t in enumerate(conf_threshs)]
+
+
+def _pooled_rows(conf_threshs, counts, H, W):
+    """Rows of particle_set_sweep_pooled.tsv: per threshold, ``_scores`` of the pixel counts
+    summed over all pairs (np.int64) on the summed mask area, then the three sums."""
+    area = sum(int(h) * int(w) for h, w in zip(H, W))
+    tot = np.asarray(counts, dtype=np.int64).reshape(-1, len(conf_threshs), 3).sum(
+        axis=0, dtype=np.int64)
+    return [(repr(float(t)),) + _scores(tot[j], area, 1) + tuple(tot[j])
+            for j, t in enumerate(conf_threshs)]
+
+
+def _write_tsv(path, header, rows):
+    with open(path, "wt") as o:
+        o.write("\t".join(header) + "\n")
+        for e in rows:
+            o.write("\t".join(str(v) for v in e) + "\n")
+
+
+def write_sweep_tsv(path, names, conf_threshs, counts, H, W):
+    _write_tsv(path, ["filename", "conf_thresh", "precision", "recall", "f1", "pos_frac"],
+               _sweep_rows(names, conf_threshs, counts, H, W))
+
+
+def write_sweep_pooled_tsv(path, conf_threshs, counts, H, W):
+    _write_tsv(path, ["conf_thresh", "precision", "recall", "f1", "pos_frac", "gt_pixels",
+                      "picked_pixels", "tp_pixels"], _pooled_rows(conf_threshs, counts, H, W))
 
 
 def get_segmentation_scores(gt_boxes, pckr_boxes, conf_thresh=None, mrc_w=None, mrc_h=None):
@@ -175,7 +308,7 @@ def read_box_file(path):
     return np.stack(cols[:5], axis=1) if len(df) else np.zeros((0, 5))
 
 
-def main(argv=None):
+def _parser():
     ap = argparse.ArgumentParser(
         description="Score detections between ground truth and particle picker coordinate "
                     "sets, matching files by name (BOX format).")
@@ -186,7 +319,16 @@ def main(argv=None):
     ap.add_argument("--width", help="Micrograph width (pixels)", type=int, default=None)
     ap.add_argument("--verbose", help="Print individual boxfile pair scores", action="store_true")
     ap.add_argument("--out_dir", help="file path to output directory", type=str)
-    a = ap.parse_args(argv)
+    ap.add_argument("--sweep", help="Confidence thresholds to also score at, all from one pass "
+                    "(writes particle_set_sweep.tsv and particle_set_sweep_pooled.tsv)",
+                    type=float, nargs="+", metavar="T")
+    return ap
+
+
+def main(argv=None):
+    a = _parser().parse_args(argv)
+    if a.sweep is not None:
+        _check_threshs(a.sweep)
     # score_detections.py:87-90, including its quirk: an existing --out_dir is ignored
     if a.out_dir is not None and not os.path.exists(a.out_dir):
         os.makedirs(a.out_dir)
@@ -213,6 +355,12 @@ def main(argv=None):
         o.write("\t".join(["filename", "precision", "recall", "f1", "pos_frac"]) + "\n")
         for e in rows:
             o.write("\t".join(str(v) for v in e) + "\n")
+    if a.sweep is not None:
+        counts, H, W, _ = _sweep(pairs, a.sweep, a.width, a.height)
+        write_sweep_tsv(os.path.join(a.out_dir, "particle_set_sweep.tsv"), matches, a.sweep,
+                        counts, H, W)
+        write_sweep_pooled_tsv(os.path.join(a.out_dir, "particle_set_sweep_pooled.tsv"), a.sweep,
+                               counts, H, W)
 
 
 if __name__ == "__main__":
