@@ -150,7 +150,7 @@ int rgc_run(rgc_ctx* ctx, const rgc_batch_in* in, rgc_batch_out* out);
  * host once per clique level, so a second context on its own stream keeps the device busy
  * meanwhile), and one whose micrographs need a second pass re-runs that path inside rgc_wait.
  * Outputs stay valid until the next submit/run on the same context.  While a submitted
- * run awaits rgc_wait, rgc_submit, rgc_run, rgc_score_pairs, rgc_score_sweep and rgc_ilp_solve on the same
+ * run awaits rgc_wait, rgc_submit, rgc_run, rgc_score_pairs, rgc_score_sweep, rgc_score_match and rgc_ilp_solve on the same
  * context fail (negative return, rgc_last_error says why). */
 int rgc_submit(rgc_ctx* ctx, const rgc_batch_in* in);
 int rgc_wait(rgc_ctx* ctx, rgc_batch_out* out);
@@ -210,6 +210,34 @@ typedef struct rgc_score_sweep_in {
                               boxes[pk_off[p], pk_off[p] + keep[p*T+j]) */
 } rgc_score_sweep_in;
 int rgc_score_sweep(rgc_ctx* ctx, const rgc_score_sweep_in* in, int64_t* counts /* [n_pairs][T][3] */);
+
+/* Particle-level matching (beyond the reference): for every (ground truth, picks) pair the size
+ * of a maximum-cardinality one-to-one matching between ground-truth boxes and picks, two boxes
+ * being joined iff their exact intersection over union exceeds ji_threshold: with integer
+ * rectangles [x0, x1) x [y0, y1), I the intersection area and U the union area in int64,
+ * U > 0 and (double)I / (double)U > t, one f64 division.  A box with x1 <= x0 or y1 <= y0 is
+ * counted but never matched.  counts[p] = n_gt, n_picked, tp.  match (may be NULL) receives,
+ * for every pick in the caller's order (pair after pair), the index of its ground-truth box
+ * within the pair or -1; the matching returned is a function of the inputs alone (claims are
+ * resolved by lowest index, never by arrival).  RGC_F_TIMING records "k_score_match_count"
+ * and "k_score_match".
+ * Refused before any launch, the context staying usable: null arguments, a submitted run
+ * awaiting rgc_wait, n_pairs outside 0..INT32_MAX, negative or decreasing offsets, a threshold
+ * that is NaN or outside [0, 1), |x0| or |y0| above 2^30, x1 - x0 or y1 - y0 above 2^25, more
+ * than 2^31 - 1 boxes; refused after the count launch: more than 2^31 - 1 edges.
+ * Additive symbols: no struct changes layout and RGC_ABI_VERSION stays 11. */
+typedef struct rgc_score_match_in {
+  int64_t n_pairs;
+  const int64_t* gt_off;   /* [n_pairs + 1] pair p's ground truth: boxes[gt_off[p], gt_off[p+1]) */
+  const int64_t* pk_off;   /* [n_pairs + 1] pair p's picks (already filtered by confidence) */
+  const int32_t* boxes;    /* [n_boxes][4] x0, x1, y0, y1 (x1 = x0 + w, y1 = y0 + h) */
+  double ji_threshold;     /* finite, 0 <= t < 1 */
+  uint32_t flags;          /* RGC_F_TIMING */
+} rgc_score_match_in;
+int rgc_score_match(rgc_ctx* ctx, const rgc_score_match_in* in, int64_t* counts /* [n_pairs][3] */,
+                    int32_t* match /* [total picks] or NULL */);
+/* Host twin of the device edge test of rgc_score_match on two boxes (x0, x1, y0, y1): 1 / 0. */
+int rgc_test_iou_edge(const int32_t a[4], const int32_t b[4], double t);
 
 /* run_ilp (repic/commands/run_ilp.py:50-63): maximise w.x over binary x subject to A x <= 1,
  * exactly, for a batch of micrographs at once (rows are global box ids: micrographs never

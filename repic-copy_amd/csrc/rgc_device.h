@@ -382,6 +382,22 @@ __device__ __forceinline__ bool is_edge(double xa, double ya, double xb, double 
   return *ji > t;
 }
 
+// Edge test of the particle-level matching (rgc_match.hip; rgc_test_iou_edge is its host twin):
+// integer rectangles [x0, x1) x [y0, y1), joined iff their intersection over union exceeds t.
+// |x0|, |y0| <= 2^30 and sides <= 2^25 (the host checks), so the areas and their sum are exact
+// in int64 and in f64 (< 2^52), and the decision is ONE correctly rounded f64 division.  A box
+// without a pixel (x1 <= x0 or y1 <= y0) is never joined; two boxes with one have U > 0.
+__host__ __device__ inline bool iou_edge(int ax0, int ax1, int ay0, int ay1, int bx0, int bx1,
+                                         int by0, int by1, double t) {
+  if (ax1 <= ax0 || ay1 <= ay0 || bx1 <= bx0 || by1 <= by0) return false;
+  const int64_t ix = (int64_t)(ax1 < bx1 ? ax1 : bx1) - (int64_t)(ax0 > bx0 ? ax0 : bx0);
+  const int64_t iy = (int64_t)(ay1 < by1 ? ay1 : by1) - (int64_t)(ay0 > by0 ? ay0 : by0);
+  const int64_t I = (ix > 0 ? ix : 0) * (iy > 0 ? iy : 0);
+  const int64_t U = ((int64_t)ax1 - ax0) * ((int64_t)ay1 - ay0) +
+                    ((int64_t)bx1 - bx0) * ((int64_t)by1 - by0) - I;
+  return U > 0 && (double)I / (double)U > t;
+}
+
 // Compare-exchange networks on register arrays (fully unrolled: no scratch).  Batcher's
 // odd-even merge sort on the next power of two, comparators that touch the padding (+inf
 // slots above N, never moved) dropped; WANT_MID keeps only the comparators the middle

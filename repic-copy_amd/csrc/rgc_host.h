@@ -51,6 +51,9 @@ enum DevBufId {
   D_SC_BOX, D_SC_GOFF, D_SC_POFF, D_SC_TP, D_SC_TR, D_SC_TW, D_SC_CNT,
   // ... and its threshold sweep's keep table
   D_SC_KEEP,
+  // particle-level matching (rgc_match.hip): layout, per-box state, per-pair edges and results
+  D_MT_BOX, D_MT_BASE, D_MT_NGT, D_MT_WMAX, D_MT_STATE, D_MT_ETOT, D_MT_EBASE, D_MT_ADJ, D_MT_TP,
+  D_MT_STAT,
   // run_ilp set packing
   D_IL_CPTR, D_IL_ROW, D_IL_W, D_IL_REP, D_IL_PAR, D_IL_ROOT, D_IL_CSIZE, D_IL_RCNT, D_IL_RCUR,
   D_IL_RPTR, D_IL_RCOLS, D_IL_CID, D_IL_CN, D_IL_COFF, D_IL_CCUR, D_IL_MEM, D_IL_LOC, D_IL_SCR,

@@ -363,6 +363,33 @@ void launch_score_raster(hipStream_t stream, int n_tiles, const ScoreArgs& A);
 void launch_score_sweep(hipStream_t stream, int n_tiles, const ScoreArgs& A, int T,
                         const int64_t* keep);
 
+// particle-level matching (rgc_match.hip): one workgroup per pair.  Pair p's boxes are
+// boxes[base[p], base[p + 1]): its n_gt[p] ground-truth boxes, ascending in x0, then its picks.
+// Every per-box array below is indexed like boxes.
+struct MatchArgs {
+  const int4* boxes;          // x0, x1, y0, y1
+  const int64_t* base;        // [n_pairs + 1]
+  const int32_t* n_gt;        // [n_pairs]
+  const int32_t* gt_wmax;     // [n_pairs] widest ground-truth box of the pair (0: none has a pixel)
+  double t;                   // edge <=> iou_edge(..., t)
+  int32_t* deg;               // picks: edges (k_score_match_count)
+  int64_t* etot;              // [n_pairs] edges of the pair (k_score_match_count)
+  const int64_t* ebase;       // [n_pairs] first edge of the pair in adj (the host's scan of etot)
+  int32_t* rowp;              // picks: first edge, relative to ebase[p]
+  int32_t* adj;               // [edges] ground-truth box of the edge (index within the pair), ascending per pick
+  int32_t* mate;              // ground truth: its pick; picks: their ground-truth box; -1 free
+  int32_t* par;               // ground truth: claiming pick (lowest wins); picks: root of their tree
+  int32_t* lvl;               // BFS level at which the box was reached, -1 not yet
+  int32_t* found;             // picks: greedy proposal; roots: lowest free ground-truth box reached
+  int64_t* tp;                // [n_pairs] size of the matching
+  int32_t* status;            // [n_pairs] 0, or the MATCH_ST_* cap that was hit
+};
+constexpr int MATCH_ST_PHASES = 1;   // more phases than min(n_gt, n_picked) + 1
+constexpr int MATCH_ST_LEVELS = 2;   // more BFS levels than 2 min(n_gt, n_picked) + 2
+constexpr int MATCH_ST_WALK = 3;     // an augmenting walk longer than that, or off its tree
+void launch_match_count(hipStream_t stream, int n_pairs, const MatchArgs& A);
+void launch_match(hipStream_t stream, int n_pairs, const MatchArgs& A);
+
 // run_ilp exact set packing (rgc_ilp.hip)
 struct IlpArgs {
   int64_t n_cols, n_rows, n_comp;

@@ -1,5 +1,6 @@
 // rgc_score_host.cpp — rgc_score_pairs and rgc_score_sweep: tiling and launch of the
-// score_detections raster kernels (rgc_score.hip).
+// score_detections raster kernels (rgc_score.hip); rgc_score_match: layout, the two launches
+// and the hand-back of the particle-level matching (rgc_match.hip).
 #include <algorithm>
 
 #include "rgc_host.h"
@@ -128,6 +129,180 @@ extern "C" int rgc_score_pairs(rgc_ctx* c, const rgc_score_in* in, int64_t* coun
   if (P.np == 0) return 0;
   return score_launch(c, in, P, (size_t)P.np * 24, "k_score_raster", counts,
                       rgc::launch_score_raster);
+}
+
+// ---- particle-level matching (rgc_match.hip)
+namespace {
+
+constexpr int64_t MT_XY_MAX = (int64_t)1 << 30;     // |x0|, |y0|
+constexpr int64_t MT_SIDE_MAX = (int64_t)1 << 25;   // x1 - x0, y1 - y0
+
+// the section between two events as `name` (RGC_F_TIMING)
+int match_time(rgc_ctx* c, hipEvent_t e0, hipEvent_t e1, const char* name) {
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+  c->times.push_back(ms);
+  c->time_names.push_back(name);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int rgc_score_match(rgc_ctx* c, const rgc_score_match_in* in, int64_t* counts,
+                               int32_t* match) {
+  if (!c || !in || !counts) return fail("null argument");
+  if (c->pend) return fail("rgc_score_match: a submitted run awaits rgc_wait on this context");
+  const int64_t np = in->n_pairs;
+  if (np < 0 || np > INT32_MAX) return fail("n_pairs out of range");
+  const double t = in->ji_threshold;
+  if (!(t >= 0.0 && t < 1.0))   // (false for NaN)
+    return fail("rgc_score_match: ji_threshold must be finite and in [0, 1)");
+  c->times.clear();
+  c->time_names.clear();
+  if (np == 0) return 0;
+  if (!in->gt_off || !in->pk_off) return fail("null argument");
+  if (in->gt_off[0] < 0 || in->pk_off[0] < 0) return fail("negative box offset");
+  int64_t nb = 0;
+  for (int64_t p = 0; p < np; ++p) {
+    if (in->gt_off[p + 1] < in->gt_off[p] || in->pk_off[p + 1] < in->pk_off[p])
+      return fail("box offsets must be non-decreasing");
+    const int64_t dg = in->gt_off[p + 1] - in->gt_off[p], dk = in->pk_off[p + 1] - in->pk_off[p];
+    if (dg <= INT32_MAX && dk <= INT32_MAX) nb += dg + dk;
+    if (dg > INT32_MAX || dk > INT32_MAX || nb > INT32_MAX) return fail("rgc_score_match: more than 2^31 - 1 boxes in one call");
+  }
+  if (nb && !in->boxes) return fail("null argument");
+  // the device layout: pair after pair, its ground truth ascending in x0 (ties: the caller's
+  // order), then its picks; perm = the caller's index of each sorted ground-truth box
+  std::vector<int32_t> box((size_t)nb * 4), perm((size_t)nb), ngt((size_t)np), wmax((size_t)np);
+  std::vector<int64_t> base((size_t)np + 1);
+  std::vector<int32_t> idx;
+  int64_t at = 0;
+  for (int64_t p = 0; p < np; ++p) {
+    base[p] = at;
+    const int64_t g0 = in->gt_off[p], ng = in->gt_off[p + 1] - g0;
+    const int64_t k0 = in->pk_off[p], nk = in->pk_off[p + 1] - k0;
+    for (int which = 0; which < 2; ++which) {
+      const int64_t b0 = which ? k0 : g0, n = which ? nk : ng;
+      for (int64_t b = b0; b < b0 + n; ++b) {
+        const int32_t* q = in->boxes + 4 * b;
+        if (q[0] > MT_XY_MAX || q[0] < -MT_XY_MAX || q[2] > MT_XY_MAX || q[2] < -MT_XY_MAX ||
+            (int64_t)q[1] - q[0] > MT_SIDE_MAX || (int64_t)q[3] - q[2] > MT_SIDE_MAX)
+          return fail("rgc_score_match: box " + std::to_string(b) +
+                      " is out of range (|x0|, |y0| <= 2^30, sides <= 2^25)");
+      }
+    }
+    idx.resize((size_t)ng);
+    for (int64_t i = 0; i < ng; ++i) idx[i] = (int32_t)i;
+    const int32_t* gb = in->boxes + 4 * g0;
+    std::stable_sort(idx.begin(), idx.end(),
+                     [gb](int32_t a, int32_t b) { return gb[4 * a] < gb[4 * b]; });
+    int32_t wm = 0;
+    for (int64_t i = 0; i < ng; ++i) {
+      const int32_t* q = gb + 4 * idx[i];
+      std::copy(q, q + 4, box.begin() + 4 * (at + i));
+      perm[at + i] = idx[i];
+      if (q[1] > q[0] && q[3] > q[2]) wm = std::max<int32_t>(wm, q[1] - q[0]);
+    }
+    if (nk) std::copy(in->boxes + 4 * k0, in->boxes + 4 * (k0 + nk), box.begin() + 4 * (at + ng));
+    ngt[p] = (int32_t)ng;
+    wmax[p] = wm;
+    at += ng + nk;
+  }
+  base[np] = at;
+
+  HIPCHK(hipSetDevice(c->device));
+  const size_t nbz = (size_t)nb;
+  TRY(ensure_dev(c, D_MT_BOX, nbz * 16));
+  TRY(ensure_dev(c, D_MT_BASE, (size_t)(np + 1) * 8));
+  TRY(ensure_dev(c, D_MT_NGT, (size_t)np * 4));
+  TRY(ensure_dev(c, D_MT_WMAX, (size_t)np * 4));
+  TRY(ensure_dev(c, D_MT_STATE, nbz * 4 * 6));   // deg, rowp, mate, par, lvl, found
+  TRY(ensure_dev(c, D_MT_ETOT, (size_t)np * 8));
+  TRY(ensure_dev(c, D_MT_EBASE, (size_t)np * 8));
+  TRY(ensure_dev(c, D_MT_TP, (size_t)np * 8));
+  TRY(ensure_dev(c, D_MT_STAT, (size_t)np * 4));
+  hipStream_t s = c->stream;
+  if (nb) HIPCHK(hipMemcpyAsync(c->d[D_MT_BOX].p, box.data(), nbz * 16, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(c->d[D_MT_BASE].p, base.data(), (size_t)(np + 1) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(c->d[D_MT_NGT].p, ngt.data(), (size_t)np * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(c->d[D_MT_WMAX].p, wmax.data(), (size_t)np * 4, hipMemcpyHostToDevice, s));
+  rgc::MatchArgs A{};
+  A.boxes = D<int4>(c, D_MT_BOX);
+  A.base = D<int64_t>(c, D_MT_BASE);
+  A.n_gt = D<int32_t>(c, D_MT_NGT);
+  A.gt_wmax = D<int32_t>(c, D_MT_WMAX);
+  A.t = t;
+  int32_t* st = D<int32_t>(c, D_MT_STATE);
+  A.deg = st;
+  A.rowp = st + nbz;
+  A.mate = st + 2 * nbz;
+  A.par = st + 3 * nbz;
+  A.lvl = st + 4 * nbz;
+  A.found = st + 5 * nbz;
+  A.etot = D<int64_t>(c, D_MT_ETOT);
+  A.ebase = D<int64_t>(c, D_MT_EBASE);
+  A.tp = D<int64_t>(c, D_MT_TP);
+  A.status = D<int32_t>(c, D_MT_STAT);
+  const bool timing = (in->flags & RGC_F_TIMING) != 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (timing)
+    for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  // the count launch; its per-pair totals size the edge lists
+  if (timing) HIPCHK(hipEventRecord(ev[0], s));
+  rgc::launch_match_count(s, (int)np, A);
+  HIPCHK(hipGetLastError());
+  if (timing) HIPCHK(hipEventRecord(ev[1], s));
+  std::vector<int64_t> etot((size_t)np), ebase((size_t)np);
+  HIPCHK(hipMemcpyAsync(etot.data(), c->d[D_MT_ETOT].p, (size_t)np * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  int64_t ne = 0;
+  for (int64_t p = 0; p < np; ++p) {
+    ebase[p] = ne;
+    ne += etot[p];
+    if (etot[p] < 0 || ne > INT32_MAX) {
+      if (timing)
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+      return fail("rgc_score_match: more than 2^31 - 1 edges in one call");
+    }
+  }
+  TRY(ensure_dev(c, D_MT_ADJ, (size_t)ne * 4));
+  A.adj = D<int32_t>(c, D_MT_ADJ);
+  HIPCHK(hipMemcpyAsync(c->d[D_MT_EBASE].p, ebase.data(), (size_t)np * 8, hipMemcpyHostToDevice, s));
+  if (timing) HIPCHK(hipEventRecord(ev[2], s));
+  rgc::launch_match(s, (int)np, A);
+  HIPCHK(hipGetLastError());
+  if (timing) HIPCHK(hipEventRecord(ev[3], s));
+  std::vector<int64_t> tp((size_t)np);
+  std::vector<int32_t> status((size_t)np), mate;
+  HIPCHK(hipMemcpyAsync(tp.data(), c->d[D_MT_TP].p, (size_t)np * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(status.data(), c->d[D_MT_STAT].p, (size_t)np * 4, hipMemcpyDeviceToHost, s));
+  if (match && nb) {
+    mate.resize(nbz);
+    HIPCHK(hipMemcpyAsync(mate.data(), A.mate, nbz * 4, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  if (timing) {
+    TRY(match_time(c, ev[0], ev[1], "k_score_match_count"));
+    TRY(match_time(c, ev[2], ev[3], "k_score_match"));
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+  int64_t out = 0;
+  for (int64_t p = 0; p < np; ++p) {
+    if (status[p] != 0)
+      return fail("rgc_score_match: pair " + std::to_string(p) + " ran into a loop bound (status " +
+                  std::to_string(status[p]) + ")");
+    const int64_t ng = ngt[p], nk = base[p + 1] - base[p] - ng;
+    counts[3 * p] = ng;
+    counts[3 * p + 1] = nk;
+    counts[3 * p + 2] = tp[p];
+    if (match)
+      for (int64_t u = 0; u < nk; ++u) {
+        const int32_t g = mate[base[p] + ng + u];
+        match[out + u] = g < 0 ? -1 : perm[base[p] + g];
+      }
+    out += nk;
+  }
+  return 0;
 }
 
 extern "C" int rgc_score_sweep(rgc_ctx* c, const rgc_score_sweep_in* in, int64_t* counts) {

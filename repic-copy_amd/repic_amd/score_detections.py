@@ -13,6 +13,11 @@ Beyond the reference: ``score_sweep`` / ``sweep_counts`` give what ``score_pairs
 of a list of confidence thresholds from one launch that paints every box once
 (``rgc_score_sweep``), and ``--sweep T [T ...]`` writes those curves per file
 (``particle_set_sweep.tsv``) and pooled over all files (``particle_set_sweep_pooled.tsv``).
+``match_pairs`` / ``match_scores`` give the particle-level metric the picking papers report: the
+picks that hit a ground-truth particle one to one at an IoU cutoff, as the size of a
+maximum-cardinality matching found on the device for every pair of a data set in one call
+(``rgc_score_match``, rgc_match.hip); ``--match_ji T`` writes it per file
+(``particle_set_match.tsv``) and pooled (``particle_set_match_pooled.tsv``).
 """
 from __future__ import annotations
 
@@ -48,6 +53,17 @@ class ScoreSweepIn(C.Structure):
 
 _lib.lib.rgc_score_sweep.argtypes = [C.c_void_p, C.POINTER(ScoreSweepIn), C.c_void_p]
 _lib.lib.rgc_score_sweep.restype = C.c_int
+
+
+class ScoreMatchIn(C.Structure):
+    _fields_ = [("n_pairs", C.c_int64), ("gt_off", C.c_void_p), ("pk_off", C.c_void_p),
+                ("boxes", C.c_void_p), ("ji_threshold", C.c_double), ("flags", C.c_uint32)]
+
+
+_lib.lib.rgc_score_match.argtypes = [C.c_void_p, C.POINTER(ScoreMatchIn), C.c_void_p, C.c_void_p]
+_lib.lib.rgc_score_match.restype = C.c_int
+_lib.lib.rgc_test_iou_edge.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_double]
+_lib.lib.rgc_test_iou_edge.restype = C.c_int
 
 
 def _py_round(v):
@@ -271,6 +287,119 @@ def write_sweep_pooled_tsv(path, conf_threshs, counts, H, W):
                       "picked_pixels", "tp_pixels"], _pooled_rows(conf_threshs, counts, H, W))
 
 
+# ------------------------------------------------------------------ particle-level matching
+MATCH_XY_MAX = 1 << 30     # |round(x)|, |round(y)|
+MATCH_SIDE_MAX = 1 << 25   # round(w), round(h): every area and every sum exact in int64 and f64
+
+
+def iou_edge(a, b, t):
+    """Host twin of the device edge test (``rgc_test_iou_edge``) on two integer rectangles
+    (x0, x1, y0, y1): True iff both have a pixel and ``float(I) / float(U) > t``."""
+    qa = (C.c_int32 * 4)(*[int(v) for v in a])
+    qb = (C.c_int32 * 4)(*[int(v) for v in b])
+    return bool(_lib.lib.rgc_test_iou_edge(qa, qb, float(t)))
+
+
+def _match_rects(x, y, w, h):
+    """(n, 4) int32 x0, x1, y0, y1 of the rectangles [x, x + w) x [y, y + h) after Python
+    ``round()`` of each value, unclipped.  A box with round(w) < 1 or round(h) < 1 becomes the
+    empty rectangle at its corner (counted, never matched).  ValueError: non-finite values
+    (``_py_round``'s), |x|, |y| above 2^30, w, h above 2^25."""
+    xi, yi, wi, hi = (_py_round(np.clip(_finite(v), -2.0 ** 62, 2.0 ** 62)) for v in (x, y, w, h))
+    if len(xi) and (np.abs(xi).max() > MATCH_XY_MAX or np.abs(yi).max() > MATCH_XY_MAX):
+        raise ValueError("box coordinates beyond +-2^30 after rounding")
+    if len(xi) and (wi.max() > MATCH_SIDE_MAX or hi.max() > MATCH_SIDE_MAX):
+        raise ValueError("box sizes beyond 2^25 after rounding")
+    none = (wi < 1) | (hi < 1)
+    wi, hi = np.where(none, 0, wi), np.where(none, 0, hi)
+    return np.stack([xi, xi + wi, yi, yi + hi], axis=1).astype(np.int32)
+
+
+def _finite(v):
+    """``v`` as float64, with ``_py_round``'s ValueError for NaN or infinity."""
+    v = np.asarray(v, dtype=np.float64)
+    if not np.isfinite(v).all():
+        raise ValueError("cannot convert float NaN or infinity to integer")
+    return v
+
+
+def _prf(n_gt, n_picked, tp):
+    """(precision, recall, f1) of the counts as Python floats; 0.0 at a zero denominator."""
+    n_gt, n_picked, tp = int(n_gt), int(n_picked), int(tp)
+    prec = tp / n_picked if n_picked else 0.0
+    rec = tp / n_gt if n_gt else 0.0
+    f1 = 2 * prec * rec / (prec + rec) if prec + rec else 0.0
+    return prec, rec, f1
+
+
+def match_pairs(pairs, ji_thresh, conf_thresh=None, ctx=None, timing=False, assignment=False):
+    """Particle-level true positives of every (gt_boxes, pckr_boxes) pair in one device call:
+    an (n_pairs, 3) int64 array of n_gt, n_picked (picks with ``conf < conf_thresh`` dropped,
+    as in ``score_pairs``) and tp, the size of a maximum-cardinality one-to-one matching in
+    which a ground-truth box and a pick can be joined iff the IoU of their rounded, unclipped
+    rectangles exceeds ``ji_thresh`` (finite, 0 <= t < 1).  With ``assignment`` also a list of
+    int32 arrays, one per pair over its kept picks in the caller's order: the index of the
+    pick's ground-truth box within the pair, or -1 (the same arrays on every run); with
+    ``timing`` also the kernel ms, last.  Bad values raise ValueError before any device work."""
+    t = _lib.check_ji_threshold(ji_thresh)
+    gts, pks = [], []
+    for gt, pk in pairs:
+        g = _as_cols(gt)
+        p = _as_cols(pk)
+        if conf_thresh is not None:
+            keep = ~(np.asarray(p[4], dtype=np.float64) < conf_thresh)
+            p = tuple(np.asarray(c)[keep] for c in p)
+        gts.append(_match_rects(*g[:4]))
+        pks.append(_match_rects(*p[:4]))
+    npairs = len(gts)
+    z = np.zeros((0, 4), np.int32)
+    boxes = np.ascontiguousarray(np.concatenate(gts + pks + [z]), dtype=np.int32)
+    gt_off = np.cumsum([0] + [len(v) for v in gts]).astype(np.int64)
+    pk_off = (gt_off[-1] + np.cumsum([0] + [len(v) for v in pks])).astype(np.int64)
+    counts = np.zeros((npairs, 3), dtype=np.int64)
+    match = np.full(int(pk_off[-1] - pk_off[0]), -1, dtype=np.int32)
+    mi = ScoreMatchIn(npairs, gt_off.ctypes.data, pk_off.ctypes.data, boxes.ctypes.data, t,
+                      _lib.F_TIMING if timing else 0)
+    ctx = ctx or _ctx()
+    ctx._retire()   # a live Result of an earlier run keeps its host buffers
+    _lib._check(_lib.lib.rgc_score_match(ctx._p, C.byref(mi), counts.ctypes.data,
+                                         match.ctypes.data if assignment else None))
+    out = (counts,)
+    if assignment:
+        lo = pk_off - pk_off[0]
+        out += ([match[lo[i]:lo[i + 1]].copy() for i in range(npairs)],)
+    if timing:
+        out += (dict(ctx.kernel_times()),)
+    return out if len(out) > 1 else counts
+
+
+def match_scores(pairs, ji_thresh, conf_thresh=None, ctx=None):
+    """``match_pairs`` as scores: per pair (precision, recall, f1, tp, n_gt, n_picked) with
+    precision = tp / n_picked, recall = tp / n_gt, f1 = 2 p r / (p + r), each 0.0 where its
+    denominator is zero."""
+    counts = match_pairs(pairs, ji_thresh, conf_thresh, ctx)
+    return [_prf(g, k, tp) + (int(tp), int(g), int(k)) for g, k, tp in counts.tolist()]
+
+
+_MATCH_COLS = ["ji_thresh", "n_gt", "n_picked", "tp", "precision", "recall", "f1"]
+
+
+def _match_row(ji_thresh, c):
+    g, k, tp = (int(v) for v in c)
+    return (repr(float(ji_thresh)), g, k, tp) + _prf(g, k, tp)
+
+
+def write_match_tsv(path, names, ji_thresh, counts):
+    _write_tsv(path, ["filename"] + _MATCH_COLS,
+               [(m,) + _match_row(ji_thresh, counts[i]) for i, m in enumerate(names)])
+
+
+def write_match_pooled_tsv(path, ji_thresh, counts):
+    """One row from the counts summed over all pairs."""
+    tot = np.asarray(counts, dtype=np.int64).reshape(-1, 3).sum(axis=0, dtype=np.int64)
+    _write_tsv(path, _MATCH_COLS, [_match_row(ji_thresh, tot)])
+
+
 def get_segmentation_scores(gt_boxes, pckr_boxes, conf_thresh=None, mrc_w=None, mrc_h=None):
     """score_detections.py:16-48 for one pair (prec, rec, f1, pos_frac)."""
     return score_pairs([(gt_boxes, pckr_boxes)], conf_thresh, mrc_w, mrc_h)[0]
@@ -322,6 +451,11 @@ def _parser():
     ap.add_argument("--sweep", help="Confidence thresholds to also score at, all from one pass "
                     "(writes particle_set_sweep.tsv and particle_set_sweep_pooled.tsv)",
                     type=float, nargs="+", metavar="T")
+    ap.add_argument("--match_ji", help="Also score particle by particle: picks matched one to "
+                    "one to ground-truth boxes whose IoU exceeds T (0 <= T < 1), at the -c "
+                    "confidence threshold only, not at the --sweep thresholds; --height / "
+                    "--width do not apply (writes particle_set_match.tsv and "
+                    "particle_set_match_pooled.tsv)", type=float, metavar="T")
     return ap
 
 
@@ -329,6 +463,8 @@ def main(argv=None):
     a = _parser().parse_args(argv)
     if a.sweep is not None:
         _check_threshs(a.sweep)
+    if a.match_ji is not None:
+        _lib.check_ji_threshold(a.match_ji)
     # score_detections.py:87-90, including its quirk: an existing --out_dir is ignored
     if a.out_dir is not None and not os.path.exists(a.out_dir):
         os.makedirs(a.out_dir)
@@ -361,6 +497,12 @@ def main(argv=None):
                         counts, H, W)
         write_sweep_pooled_tsv(os.path.join(a.out_dir, "particle_set_sweep_pooled.tsv"), a.sweep,
                                counts, H, W)
+    if a.match_ji is not None:
+        counts = match_pairs(pairs, a.match_ji, a.c)
+        write_match_tsv(os.path.join(a.out_dir, "particle_set_match.tsv"), matches, a.match_ji,
+                        counts)
+        write_match_pooled_tsv(os.path.join(a.out_dir, "particle_set_match_pooled.tsv"),
+                               a.match_ji, counts)
 
 
 if __name__ == "__main__":
