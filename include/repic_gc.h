@@ -150,7 +150,7 @@ int rgc_run(rgc_ctx* ctx, const rgc_batch_in* in, rgc_batch_out* out);
  * host once per clique level, so a second context on its own stream keeps the device busy
  * meanwhile), and one whose micrographs need a second pass re-runs that path inside rgc_wait.
  * Outputs stay valid until the next submit/run on the same context.  While a submitted
- * run awaits rgc_wait, rgc_submit, rgc_run, rgc_score_pairs, rgc_score_sweep, rgc_score_match and rgc_ilp_solve on the same
+ * run awaits rgc_wait, rgc_submit, rgc_run, rgc_score_pairs, rgc_score_sweep, rgc_score_match, rgc_score_match_sweep and rgc_ilp_solve on the same
  * context fail (negative return, rgc_last_error says why). */
 int rgc_submit(rgc_ctx* ctx, const rgc_batch_in* in);
 int rgc_wait(rgc_ctx* ctx, rgc_batch_out* out);
@@ -236,6 +236,28 @@ typedef struct rgc_score_match_in {
 } rgc_score_match_in;
 int rgc_score_match(rgc_ctx* ctx, const rgc_score_match_in* in, int64_t* counts /* [n_pairs][3] */,
                     int32_t* match /* [total picks] or NULL */);
+/* Particle-level matching at every confidence threshold of a sweep (the precision / recall
+ * curve): what rgc_score_match returns for the picks kept at each of n_thr ascending thresholds,
+ * from one call that lays the pairs out, counts the edges and builds the edge lists once
+ * (k_score_match_sweep).  The caller orders each pair's picks so that the ones kept at threshold
+ * j are a prefix and gives the prefix lengths, as for rgc_score_sweep.  The kernel walks the
+ * thresholds from the strictest to the loosest, keeps the matching of the step before and
+ * augments it from the picks that are new at the step.  counts[p][j] = n_gt, keep[p][j], tp at
+ * threshold j; no assignment is returned.  RGC_F_TIMING (pairs.flags) records
+ * "k_score_match_count" and "k_score_match_sweep".
+ * Refused before any launch, the context staying usable: whatever rgc_score_match refuses, n_thr
+ * outside 1..RGC_MATCH_MAX_THR, a null keep with n_pairs > 0, a keep that is negative, larger
+ * than the pair's pick count or increasing in j, a submitted run awaiting rgc_wait.
+ * An additive symbol: no struct changes layout and RGC_ABI_VERSION stays 11. */
+#define RGC_MATCH_MAX_THR 1024
+typedef struct rgc_score_match_sweep_in {
+  rgc_score_match_in pairs;  /* as for rgc_score_match; each pair's picks ordered so that the
+                                picks kept at threshold j are a prefix */
+  int32_t n_thr;             /* T, 1..RGC_MATCH_MAX_THR */
+  const int64_t* keep;       /* [n_pairs * T], non-increasing in j, 0 <= keep <= the pair's picks */
+} rgc_score_match_sweep_in;
+int rgc_score_match_sweep(rgc_ctx* ctx, const rgc_score_match_sweep_in* in,
+                          int64_t* counts /* [n_pairs][T][3] */);
 /* Host twin of the device edge test of rgc_score_match on two boxes (x0, x1, y0, y1): 1 / 0. */
 int rgc_test_iou_edge(const int32_t a[4], const int32_t b[4], double t);
 

@@ -54,6 +54,8 @@ enum DevBufId {
   // particle-level matching (rgc_match.hip): layout, per-box state, per-pair edges and results
   D_MT_BOX, D_MT_BASE, D_MT_NGT, D_MT_WMAX, D_MT_STATE, D_MT_ETOT, D_MT_EBASE, D_MT_ADJ, D_MT_TP,
   D_MT_STAT,
+  // ... and its threshold sweep's keep table and per-threshold sizes
+  D_MT_KEEP, D_MT_TPS,
   // run_ilp set packing
   D_IL_CPTR, D_IL_ROW, D_IL_W, D_IL_REP, D_IL_PAR, D_IL_ROOT, D_IL_CSIZE, D_IL_RCNT, D_IL_RCUR,
   D_IL_RPTR, D_IL_RCOLS, D_IL_CID, D_IL_CN, D_IL_COFF, D_IL_CCUR, D_IL_MEM, D_IL_LOC, D_IL_SCR,

@@ -389,6 +389,11 @@ constexpr int MATCH_ST_LEVELS = 2;   // more BFS levels than 2 min(n_gt, n_picke
 constexpr int MATCH_ST_WALK = 3;     // an augmenting walk longer than that, or off its tree
 void launch_match_count(hipStream_t stream, int n_pairs, const MatchArgs& A);
 void launch_match(hipStream_t stream, int n_pairs, const MatchArgs& A);
+// the matching at each of n_thr thresholds (k_score_match_sweep): pair p's picks are ordered so
+// that the first keep[p * n_thr + j] are kept at threshold j (non-increasing in j);
+// tp_out[p * n_thr + j] = the size of the matching of those picks.  A.tp is not written.
+void launch_match_sweep(hipStream_t stream, int n_pairs, const MatchArgs& A, int n_thr,
+                        const int64_t* keep, int64_t* tp_out);
 
 // run_ilp exact set packing (rgc_ilp.hip)
 struct IlpArgs {

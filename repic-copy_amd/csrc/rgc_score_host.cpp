@@ -1,6 +1,6 @@
 // rgc_score_host.cpp — rgc_score_pairs and rgc_score_sweep: tiling and launch of the
-// score_detections raster kernels (rgc_score.hip); rgc_score_match: layout, the two launches
-// and the hand-back of the particle-level matching (rgc_match.hip).
+// score_detections raster kernels (rgc_score.hip); rgc_score_match and rgc_score_match_sweep:
+// layout, the two launches and the hand-back of the particle-level matching (rgc_match.hip).
 #include <algorithm>
 
 #include "rgc_host.h"
@@ -146,19 +146,33 @@ int match_time(rgc_ctx* c, hipEvent_t e0, hipEvent_t e1, const char* name) {
   return 0;
 }
 
-}  // namespace
+// What rgc_score_match and rgc_score_match_sweep share: the checked call, its device layout on
+// the host, the kernels' arguments and the events of a timed call.
+struct MatchPlan {
+  int64_t np = 0, nb = 0;
+  std::vector<int32_t> box, perm, ngt, wmax;   // perm: the caller's index of each sorted box
+  std::vector<int64_t> base, ebase;            // ebase: uploaded by a copy the caller waits for
+  rgc::MatchArgs A{};
+  bool timing = false;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  ~MatchPlan() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
 
-extern "C" int rgc_score_match(rgc_ctx* c, const rgc_score_match_in* in, int64_t* counts,
-                               int32_t* match) {
-  if (!c || !in || !counts) return fail("null argument");
-  if (c->pend) return fail("rgc_score_match: a submitted run awaits rgc_wait on this context");
+// Checks `in` and lays the pairs out; no device work.  np == 0 leaves the plan empty (the
+// caller returns 0).  Messages name `who`.
+int match_layout(rgc_ctx* c, const rgc_score_match_in* in, const std::string& who, MatchPlan& P) {
+  if (c->pend) return fail(who + ": a submitted run awaits rgc_wait on this context");
   const int64_t np = in->n_pairs;
   if (np < 0 || np > INT32_MAX) return fail("n_pairs out of range");
   const double t = in->ji_threshold;
   if (!(t >= 0.0 && t < 1.0))   // (false for NaN)
-    return fail("rgc_score_match: ji_threshold must be finite and in [0, 1)");
+    return fail(who + ": ji_threshold must be finite and in [0, 1)");
   c->times.clear();
   c->time_names.clear();
+  P.np = np;
   if (np == 0) return 0;
   if (!in->gt_off || !in->pk_off) return fail("null argument");
   if (in->gt_off[0] < 0 || in->pk_off[0] < 0) return fail("negative box offset");
@@ -168,17 +182,21 @@ extern "C" int rgc_score_match(rgc_ctx* c, const rgc_score_match_in* in, int64_t
       return fail("box offsets must be non-decreasing");
     const int64_t dg = in->gt_off[p + 1] - in->gt_off[p], dk = in->pk_off[p + 1] - in->pk_off[p];
     if (dg <= INT32_MAX && dk <= INT32_MAX) nb += dg + dk;
-    if (dg > INT32_MAX || dk > INT32_MAX || nb > INT32_MAX) return fail("rgc_score_match: more than 2^31 - 1 boxes in one call");
+    if (dg > INT32_MAX || dk > INT32_MAX || nb > INT32_MAX) return fail(who + ": more than 2^31 - 1 boxes in one call");
   }
   if (nb && !in->boxes) return fail("null argument");
   // the device layout: pair after pair, its ground truth ascending in x0 (ties: the caller's
   // order), then its picks; perm = the caller's index of each sorted ground-truth box
-  std::vector<int32_t> box((size_t)nb * 4), perm((size_t)nb), ngt((size_t)np), wmax((size_t)np);
-  std::vector<int64_t> base((size_t)np + 1);
+  P.nb = nb;
+  P.box.resize((size_t)nb * 4);
+  P.perm.resize((size_t)nb);
+  P.ngt.resize((size_t)np);
+  P.wmax.resize((size_t)np);
+  P.base.resize((size_t)np + 1);
   std::vector<int32_t> idx;
   int64_t at = 0;
   for (int64_t p = 0; p < np; ++p) {
-    base[p] = at;
+    P.base[p] = at;
     const int64_t g0 = in->gt_off[p], ng = in->gt_off[p + 1] - g0;
     const int64_t k0 = in->pk_off[p], nk = in->pk_off[p + 1] - k0;
     for (int which = 0; which < 2; ++which) {
@@ -187,7 +205,7 @@ extern "C" int rgc_score_match(rgc_ctx* c, const rgc_score_match_in* in, int64_t
         const int32_t* q = in->boxes + 4 * b;
         if (q[0] > MT_XY_MAX || q[0] < -MT_XY_MAX || q[2] > MT_XY_MAX || q[2] < -MT_XY_MAX ||
             (int64_t)q[1] - q[0] > MT_SIDE_MAX || (int64_t)q[3] - q[2] > MT_SIDE_MAX)
-          return fail("rgc_score_match: box " + std::to_string(b) +
+          return fail(who + ": box " + std::to_string(b) +
                       " is out of range (|x0|, |y0| <= 2^30, sides <= 2^25)");
       }
     }
@@ -199,17 +217,25 @@ extern "C" int rgc_score_match(rgc_ctx* c, const rgc_score_match_in* in, int64_t
     int32_t wm = 0;
     for (int64_t i = 0; i < ng; ++i) {
       const int32_t* q = gb + 4 * idx[i];
-      std::copy(q, q + 4, box.begin() + 4 * (at + i));
-      perm[at + i] = idx[i];
+      std::copy(q, q + 4, P.box.begin() + 4 * (at + i));
+      P.perm[at + i] = idx[i];
       if (q[1] > q[0] && q[3] > q[2]) wm = std::max<int32_t>(wm, q[1] - q[0]);
     }
-    if (nk) std::copy(in->boxes + 4 * k0, in->boxes + 4 * (k0 + nk), box.begin() + 4 * (at + ng));
-    ngt[p] = (int32_t)ng;
-    wmax[p] = wm;
+    if (nk) std::copy(in->boxes + 4 * k0, in->boxes + 4 * (k0 + nk), P.box.begin() + 4 * (at + ng));
+    P.ngt[p] = (int32_t)ng;
+    P.wmax[p] = wm;
     at += ng + nk;
   }
-  base[np] = at;
+  P.base[np] = at;
+  P.A.t = t;
+  P.timing = (in->flags & RGC_F_TIMING) != 0;
+  return 0;
+}
 
+// Uploads the layout, runs the count launch (between ev[0] and ev[1] of a timed call), sizes
+// the edge lists from its per-pair totals and uploads their bases: P.A is then complete.
+int match_count(rgc_ctx* c, const std::string& who, MatchPlan& P) {
+  const int64_t np = P.np, nb = P.nb;
   HIPCHK(hipSetDevice(c->device));
   const size_t nbz = (size_t)nb;
   TRY(ensure_dev(c, D_MT_BOX, nbz * 16));
@@ -222,16 +248,15 @@ extern "C" int rgc_score_match(rgc_ctx* c, const rgc_score_match_in* in, int64_t
   TRY(ensure_dev(c, D_MT_TP, (size_t)np * 8));
   TRY(ensure_dev(c, D_MT_STAT, (size_t)np * 4));
   hipStream_t s = c->stream;
-  if (nb) HIPCHK(hipMemcpyAsync(c->d[D_MT_BOX].p, box.data(), nbz * 16, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(c->d[D_MT_BASE].p, base.data(), (size_t)(np + 1) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(c->d[D_MT_NGT].p, ngt.data(), (size_t)np * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(c->d[D_MT_WMAX].p, wmax.data(), (size_t)np * 4, hipMemcpyHostToDevice, s));
-  rgc::MatchArgs A{};
+  if (nb) HIPCHK(hipMemcpyAsync(c->d[D_MT_BOX].p, P.box.data(), nbz * 16, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(c->d[D_MT_BASE].p, P.base.data(), (size_t)(np + 1) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(c->d[D_MT_NGT].p, P.ngt.data(), (size_t)np * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(c->d[D_MT_WMAX].p, P.wmax.data(), (size_t)np * 4, hipMemcpyHostToDevice, s));
+  rgc::MatchArgs& A = P.A;
   A.boxes = D<int4>(c, D_MT_BOX);
   A.base = D<int64_t>(c, D_MT_BASE);
   A.n_gt = D<int32_t>(c, D_MT_NGT);
   A.gt_wmax = D<int32_t>(c, D_MT_WMAX);
-  A.t = t;
   int32_t* st = D<int32_t>(c, D_MT_STATE);
   A.deg = st;
   A.rowp = st + nbz;
@@ -243,35 +268,56 @@ extern "C" int rgc_score_match(rgc_ctx* c, const rgc_score_match_in* in, int64_t
   A.ebase = D<int64_t>(c, D_MT_EBASE);
   A.tp = D<int64_t>(c, D_MT_TP);
   A.status = D<int32_t>(c, D_MT_STAT);
-  const bool timing = (in->flags & RGC_F_TIMING) != 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  if (timing)
-    for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  if (P.timing)
+    for (hipEvent_t& e : P.ev) HIPCHK(hipEventCreate(&e));
   // the count launch; its per-pair totals size the edge lists
-  if (timing) HIPCHK(hipEventRecord(ev[0], s));
+  if (P.timing) HIPCHK(hipEventRecord(P.ev[0], s));
   rgc::launch_match_count(s, (int)np, A);
   HIPCHK(hipGetLastError());
-  if (timing) HIPCHK(hipEventRecord(ev[1], s));
-  std::vector<int64_t> etot((size_t)np), ebase((size_t)np);
+  if (P.timing) HIPCHK(hipEventRecord(P.ev[1], s));
+  std::vector<int64_t> etot((size_t)np);
+  P.ebase.resize((size_t)np);
   HIPCHK(hipMemcpyAsync(etot.data(), c->d[D_MT_ETOT].p, (size_t)np * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   int64_t ne = 0;
   for (int64_t p = 0; p < np; ++p) {
-    ebase[p] = ne;
+    P.ebase[p] = ne;
     ne += etot[p];
-    if (etot[p] < 0 || ne > INT32_MAX) {
-      if (timing)
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-      return fail("rgc_score_match: more than 2^31 - 1 edges in one call");
-    }
+    if (etot[p] < 0 || ne > INT32_MAX) return fail(who + ": more than 2^31 - 1 edges in one call");
   }
   TRY(ensure_dev(c, D_MT_ADJ, (size_t)ne * 4));
   A.adj = D<int32_t>(c, D_MT_ADJ);
-  HIPCHK(hipMemcpyAsync(c->d[D_MT_EBASE].p, ebase.data(), (size_t)np * 8, hipMemcpyHostToDevice, s));
-  if (timing) HIPCHK(hipEventRecord(ev[2], s));
+  HIPCHK(hipMemcpyAsync(c->d[D_MT_EBASE].p, P.ebase.data(), (size_t)np * 8, hipMemcpyHostToDevice, s));
+  return 0;
+}
+
+// the first pair whose status says it ran into a loop bound
+int match_status(const std::string& who, const std::vector<int32_t>& status) {
+  for (size_t p = 0; p < status.size(); ++p)
+    if (status[p] != 0)
+      return fail(who + ": pair " + std::to_string(p) + " ran into a loop bound (status " +
+                  std::to_string(status[p]) + ")");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int rgc_score_match(rgc_ctx* c, const rgc_score_match_in* in, int64_t* counts,
+                               int32_t* match) {
+  if (!c || !in || !counts) return fail("null argument");
+  const std::string who = "rgc_score_match";
+  MatchPlan P;
+  TRY(match_layout(c, in, who, P));
+  const int64_t np = P.np, nb = P.nb;
+  if (np == 0) return 0;
+  TRY(match_count(c, who, P));
+  const rgc::MatchArgs& A = P.A;
+  const size_t nbz = (size_t)nb;
+  hipStream_t s = c->stream;
+  if (P.timing) HIPCHK(hipEventRecord(P.ev[2], s));
   rgc::launch_match(s, (int)np, A);
   HIPCHK(hipGetLastError());
-  if (timing) HIPCHK(hipEventRecord(ev[3], s));
+  if (P.timing) HIPCHK(hipEventRecord(P.ev[3], s));
   std::vector<int64_t> tp((size_t)np);
   std::vector<int32_t> status((size_t)np), mate;
   HIPCHK(hipMemcpyAsync(tp.data(), c->d[D_MT_TP].p, (size_t)np * 8, hipMemcpyDeviceToHost, s));
@@ -281,27 +327,82 @@ extern "C" int rgc_score_match(rgc_ctx* c, const rgc_score_match_in* in, int64_t
     HIPCHK(hipMemcpyAsync(mate.data(), A.mate, nbz * 4, hipMemcpyDeviceToHost, s));
   }
   HIPCHK(hipStreamSynchronize(s));
-  if (timing) {
-    TRY(match_time(c, ev[0], ev[1], "k_score_match_count"));
-    TRY(match_time(c, ev[2], ev[3], "k_score_match"));
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  if (P.timing) {
+    TRY(match_time(c, P.ev[0], P.ev[1], "k_score_match_count"));
+    TRY(match_time(c, P.ev[2], P.ev[3], "k_score_match"));
   }
+  TRY(match_status(who, status));
   int64_t out = 0;
   for (int64_t p = 0; p < np; ++p) {
-    if (status[p] != 0)
-      return fail("rgc_score_match: pair " + std::to_string(p) + " ran into a loop bound (status " +
-                  std::to_string(status[p]) + ")");
-    const int64_t ng = ngt[p], nk = base[p + 1] - base[p] - ng;
+    const int64_t ng = P.ngt[p], nk = P.base[p + 1] - P.base[p] - ng;
     counts[3 * p] = ng;
     counts[3 * p + 1] = nk;
     counts[3 * p + 2] = tp[p];
     if (match)
       for (int64_t u = 0; u < nk; ++u) {
-        const int32_t g = mate[base[p] + ng + u];
-        match[out + u] = g < 0 ? -1 : perm[base[p] + g];
+        const int32_t g = mate[P.base[p] + ng + u];
+        match[out + u] = g < 0 ? -1 : P.perm[P.base[p] + g];
       }
     out += nk;
   }
+  return 0;
+}
+
+extern "C" int rgc_score_match_sweep(rgc_ctx* c, const rgc_score_match_sweep_in* in,
+                                     int64_t* counts) {
+  if (!c || !in || !counts) return fail("null argument");
+  const std::string who = "rgc_score_match_sweep";
+  const int64_t T = in->n_thr;
+  if (T < 1 || T > RGC_MATCH_MAX_THR)
+    return fail(who + ": n_thr " + std::to_string(T) + " is outside 1.." +
+                std::to_string(RGC_MATCH_MAX_THR));
+  const rgc_score_match_in* pi = &in->pairs;
+  MatchPlan P;
+  TRY(match_layout(c, pi, who, P));
+  const int64_t np = P.np;
+  if (np == 0) return 0;
+  if (!in->keep) return fail("null argument");
+  for (int64_t p = 0; p < np; ++p) {
+    const int64_t n = pi->pk_off[p + 1] - pi->pk_off[p];
+    const int64_t* k = in->keep + p * T;
+    for (int64_t j = 0; j < T; ++j) {
+      if (k[j] < 0 || k[j] > n)
+        return fail(who + ": keep[" + std::to_string(p) + "][" + std::to_string(j) + "] = " +
+                    std::to_string(k[j]) + " is outside the pair's " + std::to_string(n) +
+                    " picks");
+      if (j && k[j] > k[j - 1])
+        return fail(who + ": keep[" + std::to_string(p) + "] increases at threshold " +
+                    std::to_string(j) + " (thresholds ascend, so keep must not)");
+    }
+  }
+  TRY(match_count(c, who, P));
+  const size_t nt = (size_t)np * (size_t)T;
+  TRY(ensure_dev(c, D_MT_KEEP, nt * 8));
+  TRY(ensure_dev(c, D_MT_TPS, nt * 8));
+  hipStream_t s = c->stream;
+  HIPCHK(hipMemcpyAsync(c->d[D_MT_KEEP].p, in->keep, nt * 8, hipMemcpyHostToDevice, s));
+  if (P.timing) HIPCHK(hipEventRecord(P.ev[2], s));
+  rgc::launch_match_sweep(s, (int)np, P.A, (int)T, D<int64_t>(c, D_MT_KEEP),
+                          D<int64_t>(c, D_MT_TPS));
+  HIPCHK(hipGetLastError());
+  if (P.timing) HIPCHK(hipEventRecord(P.ev[3], s));
+  std::vector<int64_t> tp(nt);
+  std::vector<int32_t> status((size_t)np);
+  HIPCHK(hipMemcpyAsync(tp.data(), c->d[D_MT_TPS].p, nt * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(status.data(), c->d[D_MT_STAT].p, (size_t)np * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (P.timing) {
+    TRY(match_time(c, P.ev[0], P.ev[1], "k_score_match_count"));
+    TRY(match_time(c, P.ev[2], P.ev[3], "k_score_match_sweep"));
+  }
+  TRY(match_status(who, status));
+  for (int64_t p = 0; p < np; ++p)
+    for (int64_t j = 0; j < T; ++j) {
+      int64_t* q = counts + (p * T + j) * 3;
+      q[0] = P.ngt[p];
+      q[1] = in->keep[p * T + j];
+      q[2] = tp[(size_t)(p * T + j)];
+    }
   return 0;
 }
 

@@ -18,6 +18,11 @@ picks that hit a ground-truth particle one to one at an IoU cutoff, as the size 
 maximum-cardinality matching found on the device for every pair of a data set in one call
 (``rgc_score_match``, rgc_match.hip); ``--match_ji T`` writes it per file
 (``particle_set_match.tsv``) and pooled (``particle_set_match_pooled.tsv``).
+``match_sweep`` / ``match_curve`` give that metric at every confidence threshold of a list, the
+precision / recall curve, from one device call that builds the edges once and augments the
+matching from threshold to threshold (``rgc_score_match_sweep``); ``average_precision`` is the
+area under it, and ``--match_sweep T [T ...]`` writes both (``particle_set_match_sweep.tsv``,
+``particle_set_match_sweep_pooled.tsv``).
 """
 from __future__ import annotations
 
@@ -62,6 +67,14 @@ class ScoreMatchIn(C.Structure):
 
 _lib.lib.rgc_score_match.argtypes = [C.c_void_p, C.POINTER(ScoreMatchIn), C.c_void_p, C.c_void_p]
 _lib.lib.rgc_score_match.restype = C.c_int
+
+
+class ScoreMatchSweepIn(C.Structure):
+    _fields_ = [("pairs", ScoreMatchIn), ("n_thr", C.c_int32), ("keep", C.c_void_p)]
+
+
+_lib.lib.rgc_score_match_sweep.argtypes = [C.c_void_p, C.POINTER(ScoreMatchSweepIn), C.c_void_p]
+_lib.lib.rgc_score_match_sweep.restype = C.c_int
 _lib.lib.rgc_test_iou_edge.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_double]
 _lib.lib.rgc_test_iou_edge.restype = C.c_int
 
@@ -400,6 +413,105 @@ def write_match_pooled_tsv(path, ji_thresh, counts):
     _write_tsv(path, _MATCH_COLS, [_match_row(ji_thresh, tot)])
 
 
+# ------------------------------------------- particle-level matching at every threshold
+def match_sweep(pairs, ji_thresh, conf_threshs, ctx=None, timing=False):
+    """``match_pairs`` at every confidence threshold of ``conf_threshs`` in one device call
+    (``rgc_score_match_sweep``): an (n_pairs, T, 3) int64 array of n_gt, n_picked, tp with
+    ``match_sweep(pairs, t, ts)[i, j] == match_pairs(pairs, t, conf_thresh=ts[j])[i]``, in the
+    order the thresholds were given (any order, duplicates and +-inf allowed; NaN or an empty
+    list: ValueError).  The pairs are laid out, their edges counted and listed once; the kernel
+    goes from the strictest threshold to the loosest and augments the matching of the step before
+    from the picks that are new.  A pick with a NaN confidence is kept at every threshold.  Every
+    pick's coordinates are checked, whether a threshold keeps it or not.  No assignment is
+    returned.  With ``timing`` also the kernel ms.  Bad values raise ValueError before any
+    device work."""
+    t = _lib.check_ji_threshold(ji_thresh)
+    ts = _check_threshs(conf_threshs)
+    uniq, inv = np.unique(ts, return_inverse=True)
+    gts, pks, keeps = [], [], []
+    for gt, pk in pairs:
+        g = _as_cols(gt)
+        p = _as_cols(pk)
+        order, keep = _sweep_plan(np.asarray(p[4], dtype=np.float64), uniq)
+        gts.append(_match_rects(*g[:4]))
+        pks.append(_match_rects(*p[:4])[order])
+        keeps.append(keep)
+    npairs, T = len(gts), len(uniq)
+    z = np.zeros((0, 4), np.int32)
+    boxes = np.ascontiguousarray(np.concatenate(gts + pks + [z]), dtype=np.int32)
+    gt_off = np.cumsum([0] + [len(v) for v in gts]).astype(np.int64)
+    pk_off = (gt_off[-1] + np.cumsum([0] + [len(v) for v in pks])).astype(np.int64)
+    keep = np.ascontiguousarray(np.concatenate(keeps + [np.zeros(0, np.int64)]), dtype=np.int64)
+    counts = np.zeros((npairs, T, 3), dtype=np.int64)
+    mi = ScoreMatchIn(npairs, gt_off.ctypes.data, pk_off.ctypes.data, boxes.ctypes.data, t,
+                      _lib.F_TIMING if timing else 0)
+    sw = ScoreMatchSweepIn(mi, T, keep.ctypes.data)
+    ctx = ctx or _ctx()
+    ctx._retire()   # a live Result of an earlier run keeps its host buffers
+    _lib._check(_lib.lib.rgc_score_match_sweep(ctx._p, C.byref(sw), counts.ctypes.data))
+    counts = counts[:, inv.reshape(-1), :]
+    return (counts, dict(ctx.kernel_times())) if timing else counts
+
+
+def match_curve(pairs, ji_thresh, conf_threshs, ctx=None):
+    """``match_sweep`` as scores: per pair, per threshold in the order given,
+    (precision, recall, f1, tp, n_gt, n_picked) as in ``match_scores``."""
+    counts = match_sweep(pairs, ji_thresh, conf_threshs, ctx)
+    return [[_prf(g, k, tp) + (int(tp), int(g), int(k)) for g, k, tp in c] for c in counts.tolist()]
+
+
+def average_precision(counts):
+    """Average precision of one precision / recall curve: ``counts`` is a (T, 3) array of
+    n_gt, n_picked, tp per threshold, one pair's (``match_sweep(...)[i]``) or the sums over the
+    pairs.  The distinct rows are taken in order of decreasing threshold, that is of increasing
+    n_picked, so that recall R is non-decreasing, and with P, R from ``_prf`` (0.0 at a zero
+    denominator) and R_-1 = 0
+
+        AP = sum_i (R_i - R_(i-1)) * P_i
+
+    the uninterpolated form: no precision envelope, no fixed recall grid.  A Python float."""
+    rows = sorted({(int(k), int(tp), int(g))
+                   for g, k, tp in np.asarray(counts).reshape(-1, 3).tolist()})
+    ap, last = 0.0, 0.0
+    for k, tp, g in rows:
+        prec, rec, _ = _prf(g, k, tp)
+        ap += (rec - last) * prec
+        last = rec
+    return float(ap)
+
+
+_MATCH_SWEEP_COLS = ["ji_thresh", "conf_thresh", "n_gt", "n_picked", "tp", "precision", "recall",
+                     "f1"]
+
+
+def _match_sweep_rows(ji_thresh, conf_threshs, counts):
+    """One pair's (or the pooled) rows, thresholds in the order given."""
+    rows = []
+    for t, c in zip(conf_threshs, counts):
+        g, k, tp = (int(v) for v in c)
+        rows.append((repr(float(ji_thresh)), repr(float(t)), g, k, tp) + _prf(g, k, tp))
+    return rows
+
+
+def write_match_sweep_tsv(path, names, ji_thresh, conf_threshs, counts):
+    """Rows grouped by file, thresholds in the order given."""
+    _write_tsv(path, ["filename"] + _MATCH_SWEEP_COLS,
+               [(m,) + r for i, m in enumerate(names)
+                for r in _match_sweep_rows(ji_thresh, conf_threshs, counts[i])])
+
+
+def write_match_sweep_pooled_tsv(path, ji_thresh, conf_threshs, counts):
+    """Per threshold one row from the counts summed over all pairs, then a comment line with
+    the mean of the pairs' average precisions and the average precision of the pooled curve."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1, len(conf_threshs), 3)
+    tot = counts.sum(axis=0, dtype=np.int64)
+    _write_tsv(path, _MATCH_SWEEP_COLS, _match_sweep_rows(ji_thresh, conf_threshs, tot))
+    aps = [average_precision(c) for c in counts]
+    mean = sum(aps) / len(aps) if aps else 0.0
+    with open(path, "at") as o:
+        o.write(f"# average_precision\t{mean}\t{average_precision(tot)}\n")
+
+
 def get_segmentation_scores(gt_boxes, pckr_boxes, conf_thresh=None, mrc_w=None, mrc_h=None):
     """score_detections.py:16-48 for one pair (prec, rec, f1, pos_frac)."""
     return score_pairs([(gt_boxes, pckr_boxes)], conf_thresh, mrc_w, mrc_h)[0]
@@ -453,18 +565,28 @@ def _parser():
                     type=float, nargs="+", metavar="T")
     ap.add_argument("--match_ji", help="Also score particle by particle: picks matched one to "
                     "one to ground-truth boxes whose IoU exceeds T (0 <= T < 1), at the -c "
-                    "confidence threshold only, not at the --sweep thresholds; --height / "
-                    "--width do not apply (writes particle_set_match.tsv and "
-                    "particle_set_match_pooled.tsv)", type=float, metavar="T")
+                    "confidence threshold (at a list of thresholds: --match_sweep; the --sweep "
+                    "thresholds are the pixel metric's); --height / --width do not apply "
+                    "(writes particle_set_match.tsv and particle_set_match_pooled.tsv)",
+                    type=float, metavar="T")
+    ap.add_argument("--match_sweep", help="Confidence thresholds to also match at, all from one "
+                    "device call: the particle-level precision / recall curve and its average "
+                    "precision; needs --match_ji (writes particle_set_match_sweep.tsv and "
+                    "particle_set_match_sweep_pooled.tsv)", type=float, nargs="+", metavar="T")
     return ap
 
 
 def main(argv=None):
-    a = _parser().parse_args(argv)
+    ap = _parser()
+    a = ap.parse_args(argv)
+    if a.match_sweep is not None and a.match_ji is None:
+        ap.error("--match_sweep needs --match_ji (the IoU cutoff of the matching)")
     if a.sweep is not None:
         _check_threshs(a.sweep)
     if a.match_ji is not None:
         _lib.check_ji_threshold(a.match_ji)
+    if a.match_sweep is not None:
+        _check_threshs(a.match_sweep)
     # score_detections.py:87-90, including its quirk: an existing --out_dir is ignored
     if a.out_dir is not None and not os.path.exists(a.out_dir):
         os.makedirs(a.out_dir)
@@ -503,6 +625,13 @@ def main(argv=None):
                         counts)
         write_match_pooled_tsv(os.path.join(a.out_dir, "particle_set_match_pooled.tsv"),
                                a.match_ji, counts)
+    if a.match_sweep is not None:
+        counts = match_sweep(pairs, a.match_ji, a.match_sweep)
+        write_match_sweep_tsv(os.path.join(a.out_dir, "particle_set_match_sweep.tsv"), matches,
+                              a.match_ji, a.match_sweep, counts)
+        write_match_sweep_pooled_tsv(
+            os.path.join(a.out_dir, "particle_set_match_sweep_pooled.tsv"), a.match_ji,
+            a.match_sweep, counts)
 
 
 if __name__ == "__main__":
