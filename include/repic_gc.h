@@ -20,6 +20,10 @@
  *                       files in between (ABI 10): rgc_run, the solver and the ordered picks
  *                       in one call, the per-clique arrays staying in HBM
  *   rgc_write_boxes  <- run_ilp.py:126-133 (the final <base>.box of each micrograph; ABI 10)
+ *   rgc_consensus_members, rgc_write_members
+ *                    <- what get_cliques --multi_out + run_ilp.py:93-119 are meant to give and
+ *                       never do (run_ilp raises on such inputs): per written pick its member
+ *                       from every picker, and every picker's boxes left out of the picks
  *
  * Conventions: plain pointers and sizes, no torch types.  Returns 0 on success and a
  * negative code on error (message in rgc_last_error(), thread-local).  Outputs are owned
@@ -368,6 +372,48 @@ typedef struct rgc_pick_out {
 } rgc_pick_out;
 int rgc_pick_select(rgc_ctx* ctx, const rgc_pick_in* in, rgc_pick_out* out);
 
+/* `repic consensus --members`: which box of which picker made up each written pick, and which
+ * boxes of each picker are in no written pick.  Additive symbols: no struct changes layout and
+ * RGC_ABI_VERSION stays 11; a caller finds out by symbol lookup.
+ * rgc_consensus_members does everything rgc_consensus does, on a run with RGC_F_MEMBERS forced
+ * on, then emits on the device (rgc_pick.hip k_pick_clique_mark / k_pick_members / k_pick_left)
+ * the arrays below: host memory owned by the context like the pick arrays.  Segment
+ * s = m * k + p is picker p of micrograph m.  A micrograph with status != RGC_OK has no
+ * leftovers.  The picks of a packing have disjoint members, so segment s has
+ * boxes(s) - picks(m) leftovers; if chosen columns of one micrograph share a box the call
+ * fails and says so.  With RGC_F_TIMING the section "k_pick_members" follows "k_pick_emit";
+ * h2d_bytes / d2h_bytes include these arrays (16 k B per pick, 16 B per leftover). */
+typedef struct rgc_members_out {
+  double* pmx;             /* [n_picked*k] np.rint(x) of pick i's member from picker p at i*k+p */
+  double* pmy;
+  int64_t* left_off;       /* [n_mg*k+1] leftovers of segment s: [left_off[s], left_off[s+1]) */
+  double* left_x;          /* [left_off[n_mg*k]] np.rint(x) of the segment's boxes that are in */
+  double* left_y;          /*   no written pick, in file order */
+  int32_t* in_clique;      /* [n_mg*k] distinct boxes of the segment in at least one clique */
+} rgc_members_out;
+int rgc_consensus_members(rgc_ctx* ctx, const rgc_batch_in* in, const rgc_consensus_opts* opts,
+                          rgc_consensus_out* out, rgc_members_out* mem);
+
+/* The select / scan / emit / members kernels alone, on host arrays: test hook, the counterpart
+ * of rgc_pick_select.  Every micrograph counts as RGC_OK.  Refused before any launch (the
+ * context stays usable) for null arrays, offsets that do not start at 0 or decrease, a member
+ * or consensus index outside its segment, k outside 1..8 and a run awaiting rgc_wait. */
+typedef struct rgc_pick_members_in {
+  int32_t n_mg;
+  int32_t k;
+  const int64_t* col_off;  /* [n_mg+1] columns of micrograph m */
+  const uint8_t* x;        /* [n_cols] the packing */
+  const float* conf;       /* [n_cols] */
+  const int32_t* cons;     /* [n_cols] box of the consensus coordinates (one of the members' range) */
+  const int32_t* members;  /* [n_cols*k] batch box indices, picker order */
+  const int64_t* box_off;  /* [n_mg*k+1] */
+  const double* bx;        /* [n_boxes] */
+  const double* by;
+  int64_t num_particles;   /* < 0: all */
+} rgc_pick_members_in;
+int rgc_pick_members(rgc_ctx* ctx, const rgc_pick_members_in* in, rgc_pick_out* out,
+                     rgc_members_out* mem);
+
 int rgc_parse_files(const char* const* paths, int64_t n_files, int n_threads, rgc_parsed** out);
 void rgc_parsed_free(rgc_parsed* p);
 
@@ -430,6 +476,32 @@ typedef struct rgc_box_write_in {
 } rgc_box_write_in;
 /* n_threads threads; on an I/O error returns -errno and the lowest failing micrograph. */
 int rgc_write_boxes(const rgc_box_write_in* in, int n_threads, int64_t* failed_mg);
+
+/* `repic consensus --members` writer (an additive symbol): per micrograph the <base>.box of
+ * rgc_write_boxes and then, from the same task, <base>_members.tsv - the table the reference's
+ * run_ilp.py:110-119 builds for --multi_out inputs, with exact picker columns:
+ *   header       the k picker names joined by tabs, "\n"
+ *   pick rows    row i describes .box line i: for p = 0..k-1 the member's x, y as
+ *                str(int(np.rint(v))), then the confidence as str(np.float32(v)): 2k+1 fields
+ *   leftovers    for p = 0..k-1 in turn, the segment's leftover boxes in file order: "N/A\tN/A"
+ *                in every other picker's columns, x, y in picker p's, then "0.0"
+ * Rows are joined with "\n" and the last has none.  A skipped micrograph (count -1) gets its
+ * empty .box and no .tsv. */
+typedef struct rgc_members_write_in {
+  rgc_box_write_in box;       /* the .box files, as for rgc_write_boxes */
+  int32_t k;
+  const char* header;         /* the header line without its "\n" */
+  const double* pmx;          /* [.. * k] members of pick i (an index into px) at i*k+p, rounded */
+  const double* pmy;
+  const int64_t* seg;         /* [n_mg] micrograph's first segment in left_off (skipped: unused) */
+  const int64_t* left_off;    /* leftovers of segment s: [left_off[s], left_off[s+1]) */
+  const double* left_x;       /* rounded */
+  const double* left_y;
+} rgc_members_write_in;
+/* n_threads threads; on an I/O error returns -errno, the lowest failing micrograph and in
+ * *failed_file which of its files failed (0: .box, 1: _members.tsv). */
+int rgc_write_members(const rgc_members_write_in* in, int n_threads, int64_t* failed_mg,
+                      int32_t* failed_file);
 /* str(numpy.float32(v)) (test hook of the .box confidence column): shortest round-trip float32
  * digits, positional for 1e-4 <= |v| < 1e16 (and 0), else scientific with an exponent of at
  * least two digits; returns the length. */

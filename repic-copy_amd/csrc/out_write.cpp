@@ -19,6 +19,8 @@
 // Also the BOX writer of `repic consensus` (rgc_write_boxes, reference run_ilp.py:126-133):
 //   <base>.box   "<x>\t<y>\t<box>\t<box>\t<conf>\n" per picked particle, <x> / <y> as
 //                str(int(np.rint(v))) and <conf> as str(numpy.float32(v)) print them.
+// ... and of `repic consensus --members` (rgc_write_members): the .box and, from the same
+// task, <base>_members.tsv, the table of reference run_ilp.py:110-119 with exact picker columns.
 #include <cerrno>
 #include <charconv>
 #include <cmath>
@@ -475,6 +477,105 @@ extern "C" int rgc_write_boxes(const rgc_box_write_in* in, int n_threads, int64_
   for (int t = 0; t < nt; ++t)
     if (err[(size_t)t]) {
       if (failed_mg) *failed_mg = bad[(size_t)t];
+      return err[(size_t)t];
+    }
+  return 0;
+}
+
+namespace {
+
+// the lines of micrograph m's <base>.box into o (rgc_write_boxes and rgc_write_members)
+void box_lines(std::string& o, const rgc_box_write_in& in, const std::string& box, int m) {
+  const int64_t p0 = in.pick_off[m], cnt = in.count[m];
+  for (int64_t i = 0; i < cnt; ++i) {
+    append_int(o, in.px[p0 + i]);
+    o.push_back('\t');
+    append_int(o, in.py[p0 + i]);
+    o += box;
+    o += np_float32(in.pconf[p0 + i]);
+    o.push_back('\n');
+  }
+}
+
+}  // namespace
+
+extern "C" int rgc_write_members(const rgc_members_write_in* in, int n_threads,
+                                 int64_t* failed_mg, int32_t* failed_file) {
+  if (!in || !in->box.out_dir || !in->header || in->k < 1) return -1;
+  const rgc_box_write_in& B = in->box;
+  const int n = B.n_mg, k = in->k;
+  if (failed_mg) *failed_mg = -1;
+  if (failed_file) *failed_file = 0;
+  if (n <= 0) return 0;
+  const int nt = std::max(1, std::min(n_threads, n));
+  std::vector<int> err((size_t)nt, 0), which((size_t)nt, 0);
+  std::vector<int64_t> bad((size_t)nt, -1);
+  const std::string dir = std::string(B.out_dir) + "/";
+  const std::string box = "\t" + std::to_string((long long)B.box_size) + "\t" +
+                          std::to_string((long long)B.box_size) + "\t";
+  auto work = [&](int t) {
+    std::string o;
+    const int m0 = (int)((int64_t)n * t / nt), m1 = (int)((int64_t)n * (t + 1) / nt);
+    for (int m = m0; m < m1; ++m) {
+      // the .box, then the .tsv of the same micrograph: an earlier micrograph never has one
+      // without the other
+      o.clear();
+      box_lines(o, B, box, m);
+      int e = write_file(dir + B.bases[m] + ".box", o), w = 0;
+      if (!e && B.count[m] >= 0) {
+        w = 1;
+        o.assign(in->header);
+        const int64_t p0 = B.pick_off[m], cnt = B.count[m];
+        for (int64_t i = 0; i < cnt; ++i) {
+          o.push_back('\n');
+          for (int p = 0; p < k; ++p) {
+            append_int(o, in->pmx[(p0 + i) * k + p]);
+            o.push_back('\t');
+            append_int(o, in->pmy[(p0 + i) * k + p]);
+            o.push_back('\t');
+          }
+          o += np_float32(B.pconf[p0 + i]);
+        }
+        for (int p = 0; p < k; ++p) {
+          const int64_t s = in->seg[m] + p;
+          for (int64_t j = in->left_off[s]; j < in->left_off[s + 1]; ++j) {
+            o.push_back('\n');
+            for (int q = 0; q < k; ++q) {
+              if (q == p) {
+                append_int(o, in->left_x[j]);
+                o.push_back('\t');
+                append_int(o, in->left_y[j]);
+                o.push_back('\t');
+              } else {
+                o += "N/A\tN/A\t";
+              }
+            }
+            o += "0.0";
+          }
+        }
+        // (the header's own "\n": a table without rows is the header line alone)
+        if (o.size() == strlen(in->header)) o.push_back('\n');
+        e = write_file(dir + B.bases[m] + "_members.tsv", o);
+      }
+      if (e) {
+        err[(size_t)t] = e;
+        bad[(size_t)t] = m;
+        which[(size_t)t] = w;
+        return;
+      }
+    }
+  };
+  if (nt == 1) {
+    work(0);
+  } else {
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t) th.emplace_back(work, t);
+    for (auto& x : th) x.join();
+  }
+  for (int t = 0; t < nt; ++t)
+    if (err[(size_t)t]) {
+      if (failed_mg) *failed_mg = bad[(size_t)t];
+      if (failed_file) *failed_file = which[(size_t)t];
       return err[(size_t)t];
     }
   return 0;

@@ -65,6 +65,11 @@ enum DevBufId {
   // consensus hand-off (rgc_pick.hip)
   D_PK_META, D_PK_COLMG, D_PK_SEL, D_PK_SELCNT, D_PK_PRIMAL, D_PK_OFF, D_PK_X, D_PK_PX, D_PK_PY,
   D_PK_PCONF, D_PK_PCOL, D_PK_CONF, D_PK_CX, D_PK_CY,
+  // ... and its --members stage: segment metadata (box_off, left_off, ok), the two mark arrays,
+  // member and leftover coordinates, per-segment counts (+ the bad-member flag), and the hook's
+  // uploaded cons / members
+  D_PM_META, D_PM_INPICK, D_PM_INCL, D_PM_X, D_PM_Y, D_PM_LX, D_PM_LY, D_PM_SEG, D_PM_CONS,
+  D_PM_MEMB,
   D_COUNT
 };
 enum HostBufId {
@@ -72,7 +77,10 @@ enum HostBufId {
   H_ORDER, H_EU, H_EV, H_EJIOUT,
   // consensus: per-micrograph block (metadata upload staging, then pick_off / sel_cnt /
   // primal / ilp_status / ilp_gap) and the pick arrays
-  H_PK_META, H_PK_MG, H_PK_PX, H_PK_PY, H_PK_PCONF, H_PK_PCOL, H_COUNT
+  H_PK_META, H_PK_MG, H_PK_PX, H_PK_PY, H_PK_PCONF, H_PK_PCOL,
+  // consensus --members: segment metadata staging (then left_off), member and leftover
+  // coordinates, per-segment counts
+  H_PM_META, H_PM_X, H_PM_Y, H_PM_LX, H_PM_LY, H_PM_SEG, H_COUNT
 };
 
 struct Buf {

@@ -493,4 +493,36 @@ void launch_pick_cols(hipStream_t stream, const PickArgs& A);
 void launch_pick_select(hipStream_t stream, const PickArgs& A);   // + the pick_off scan
 void launch_pick_emit(hipStream_t stream, const PickArgs& A);
 
+// consensus --members (rgc_pick.hip): after k_pick_emit, the k members of every written pick
+// and, per (micrograph, picker), the boxes that are in no written pick, in file order.  Its own
+// argument struct: the kernels of the plain path keep their arguments and their code.
+// Segment s = m * k + p holds the boxes [box_off[s], box_off[s + 1]) of picker p of micrograph m.
+struct PickMemArgs {
+  int n_mg, k;
+  int64_t n_cols, n_picked;
+  const int64_t* col_off;     // [n_mg + 1] as PickArgs
+  const int64_t* src_base;    // [n_mg] or nullptr, as PickArgs
+  const int64_t* pick_off;    // [n_mg + 1] k_pick_scan's
+  const int32_t* pcol;        // [n_picked] k_pick_emit's
+  const int32_t* members;     // [C * k] batch box index of each clique's member, picker order
+  const int64_t* box_off;     // [n_mg * k + 1]
+  const uint8_t* ok;          // [n_mg] micrograph has leftovers (status OK)
+  const double* bx;
+  const double* by;
+  const int64_t* left_off;    // [n_mg * k + 1] where segment s' leftovers go; the segment's
+                              // capacity is left_off[s + 1] - left_off[s]: nothing is written past it
+  uint8_t* in_pick;           // [n_boxes] zeroed: box is a member of a written pick
+  uint8_t* in_clique;         // [n_boxes] zeroed: box is a member of some column
+  double* pmx;                // [n_picked * k] np.rint of member p of pick i at i * k + p
+  double* pmy;
+  double* left_x;             // [left_off[n_mg * k]]
+  double* left_y;
+  int32_t* left_cnt;          // [n_mg * k] boxes of the segment not in a written pick (the host
+                              // compares it with the capacity)
+  int32_t* clique_cnt;        // [n_mg * k] boxes of the segment in some column
+  int32_t* bad;               // [1] zeroed: set when a member lies outside its segment
+};
+void launch_pick_members(hipStream_t stream, const PickMemArgs& A);   // marks + member emit
+void launch_pick_left(hipStream_t stream, const PickMemArgs& A);      // leftover compaction
+
 }  // namespace rgc

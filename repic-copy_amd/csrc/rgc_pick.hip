@@ -10,6 +10,11 @@
 //                  column ascending) - the order of run_ilp.py:121-122's stable reverse sort,
 //                  compared as floats so +0.0 == -0.0 - and the picks of rank < num_particles:
 //                  np.rint of the consensus coordinates, the confidence, the column.
+// and, only for `consensus --members`:
+//   k_pick_clique_mark  every member box of every column is "in some clique".
+//   k_pick_members      per written pick: np.rint of its k members' coordinates, picker order,
+//                       and the members' "in a written pick" marks.
+//   k_pick_left         per (micrograph, picker): the boxes in no written pick, in file order.
 // gfx950, wave64.  One 256-thread workgroup per micrograph in the per-micrograph kernels.
 #include <hip/hip_runtime.h>
 
@@ -148,7 +153,116 @@ __global__ __launch_bounds__(PK_NT) void k_pick_emit(PickArgs A) {
   }
 }
 
+// ---- consensus --members: launched only when members are asked for (PickMemArgs)
+
+// the last m with off[m] <= i (off[0] <= i < off[n]; empty ranges skipped)
+__device__ inline int range_of(const int64_t* off, int n, int64_t i) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= i) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// One thread per column: its k member boxes are "in some clique".  Every writer stores the
+// same byte value, so concurrent stores to one address need no atomic; the marks of written
+// picks live in their own array (k_pick_members).
+__global__ __launch_bounds__(PK_NT) void k_pick_clique_mark(PickMemArgs A) {
+  const int64_t c = (int64_t)blockIdx.x * PK_NT + threadIdx.x;
+  if (c >= A.n_cols) return;
+  const int m = range_of(A.col_off, A.n_mg, c);
+  const int64_t s = (A.src_base ? A.src_base[m] : A.col_off[m]) + (c - A.col_off[m]);
+  for (int p = 0; p < A.k; ++p) {
+    const int64_t b = A.members[s * A.k + p];
+    const int64_t seg = (int64_t)m * A.k + p;
+    if (b >= A.box_off[seg] && b < A.box_off[seg + 1]) A.in_clique[b] = 1;
+    else *A.bad = 1;
+  }
+}
+
+// One thread per written pick (output position i): np.rint of its k members' coordinates, and
+// the members' "in a written pick" marks.  A member outside its segment is reported, not read.
+__global__ __launch_bounds__(PK_NT) void k_pick_members(PickMemArgs A) {
+  const int64_t i = (int64_t)blockIdx.x * PK_NT + threadIdx.x;
+  if (i >= A.n_picked) return;
+  const int m = range_of(A.pick_off, A.n_mg, i);
+  const int64_t s = (A.src_base ? A.src_base[m] : A.col_off[m]) + A.pcol[i];
+  for (int p = 0; p < A.k; ++p) {
+    const int64_t b = A.members[s * A.k + p];
+    const int64_t seg = (int64_t)m * A.k + p;
+    const bool in = b >= A.box_off[seg] && b < A.box_off[seg + 1];
+    A.pmx[i * A.k + p] = in ? rint(A.bx[b]) : 0.0;
+    A.pmy[i * A.k + p] = in ? rint(A.by[b]) : 0.0;
+    if (in) A.in_pick[b] = 1;
+    else *A.bad = 1;
+  }
+}
+
+// One workgroup per segment (micrograph, picker): ordered compaction, in file order, of the
+// boxes not in a written pick (k_pick_select's ballot / popcount / per-wave offsets), cut at the
+// segment's capacity, and the counts of such boxes and of boxes in some column.
+__global__ __launch_bounds__(PK_NT) void k_pick_left(PickMemArgs A) {
+  __shared__ int s_wave[PK_WAVES], s_cl[PK_WAVES];
+  const int64_t seg = blockIdx.x;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if (!A.ok[seg / A.k]) {   // (uniform per workgroup)
+    if (t == 0) A.left_cnt[seg] = A.clique_cnt[seg] = 0;
+    return;
+  }
+  const int64_t b0 = A.box_off[seg], n = A.box_off[seg + 1] - b0;
+  const int64_t o0 = A.left_off[seg], cap = A.left_off[seg + 1] - o0;
+  int64_t base = 0, ncl = 0;
+  for (int64_t i0 = 0; i0 < n; i0 += PK_NT) {
+    const int64_t i = i0 + t;
+    const bool on = i < n && A.in_pick[b0 + i] == 0;
+    const bool cl = i < n && A.in_clique[b0 + i] != 0;
+    const unsigned long long b = __ballot(on);
+    const unsigned long long bc = __ballot(cl);
+    const int before = __popcll(b & ((1ULL << lane) - 1));
+    if (lane == 0) {
+      s_wave[wave] = __popcll(b);
+      s_cl[wave] = __popcll(bc);
+    }
+    __syncthreads();
+    int woff = 0, tot = 0, totc = 0;
+    for (int v = 0; v < PK_WAVES; ++v) {
+      if (v < wave) woff += s_wave[v];
+      tot += s_wave[v];
+      totc += s_cl[v];
+    }
+    const int64_t pos = base + woff + before;
+    if (on && pos < cap) {
+      A.left_x[o0 + pos] = rint(A.bx[b0 + i]);
+      A.left_y[o0 + pos] = rint(A.by[b0 + i]);
+    }
+    base += tot;
+    ncl += totc;
+    __syncthreads();
+  }
+  if (t == 0) {
+    A.left_cnt[seg] = (int32_t)base;
+    A.clique_cnt[seg] = (int32_t)ncl;
+  }
+}
+
 }  // namespace
+
+void launch_pick_members(hipStream_t stream, const PickMemArgs& A) {
+  if (A.n_cols > 0) {
+    const unsigned g = (unsigned)((A.n_cols + PK_NT - 1) / PK_NT);
+    hipLaunchKernelGGL(k_pick_clique_mark, dim3(g), dim3(PK_NT), 0, stream, A);
+  }
+  if (A.n_picked > 0) {
+    const unsigned g = (unsigned)((A.n_picked + PK_NT - 1) / PK_NT);
+    hipLaunchKernelGGL(k_pick_members, dim3(g), dim3(PK_NT), 0, stream, A);
+  }
+}
+
+void launch_pick_left(hipStream_t stream, const PickMemArgs& A) {
+  if (A.n_mg <= 0) return;
+  hipLaunchKernelGGL(k_pick_left, dim3((unsigned)(A.n_mg * A.k)), dim3(PK_NT), 0, stream, A);
+}
 
 void launch_pick_cols(hipStream_t stream, const PickArgs& A) {
   if (A.n_cols <= 0) return;

@@ -31,6 +31,7 @@ JI_DEFAULT = 0.3   # the reference's threshold (get_cliques.py:138)
 OK, NO_EDGES, NO_CLIQUES = 0, 1, 2
 PARSE_OK, PARSE_INDEX, PARSE_VALUE, PARSE_ASSERT, PARSE_FALLBACK, PARSE_OSERROR = range(6)
 MAX_K = 8
+MEMBERS_SUFFIX = "_members.tsv"
 
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -105,6 +106,42 @@ class BoxWriteIn(C.Structure):
                 ("pconf", C.c_void_p)]
 
 
+class MembersOut(C.Structure):
+    _fields_ = [("pmx", _f64p), ("pmy", _f64p), ("left_off", _i64p), ("left_x", _f64p),
+                ("left_y", _f64p), ("in_clique", _i32p)]
+
+
+class PickMembersIn(C.Structure):
+    _fields_ = [("n_mg", C.c_int32), ("k", C.c_int32), ("col_off", C.c_void_p),
+                ("x", C.c_void_p), ("conf", C.c_void_p), ("cons", C.c_void_p),
+                ("members", C.c_void_p), ("box_off", C.c_void_p), ("bx", C.c_void_p),
+                ("by", C.c_void_p), ("num_particles", C.c_int64)]
+
+
+class MembersWriteIn(C.Structure):
+    _fields_ = [("box", BoxWriteIn), ("k", C.c_int32), ("header", C.c_char_p),
+                ("pmx", C.c_void_p), ("pmy", C.c_void_p), ("seg", C.c_void_p),
+                ("left_off", C.c_void_p), ("left_x", C.c_void_p), ("left_y", C.c_void_p)]
+
+
+MEMBERS_SYMBOLS = ("rgc_consensus_members", "rgc_pick_members", "rgc_write_members")
+
+
+def has_members() -> bool:
+    """The loaded library has the ``consensus --members`` entry points (additive symbols: the
+    ABI version does not tell)."""
+    return all(hasattr(lib, n) for n in MEMBERS_SYMBOLS)
+
+
+if has_members():
+    lib.rgc_consensus_members.argtypes = [C.c_void_p, C.POINTER(BatchIn),
+                                          C.POINTER(ConsensusOpts), C.POINTER(ConsensusOut),
+                                          C.POINTER(MembersOut)]
+    lib.rgc_pick_members.argtypes = [C.c_void_p, C.POINTER(PickMembersIn), C.POINTER(PickOut),
+                                     C.POINTER(MembersOut)]
+    lib.rgc_write_members.argtypes = [C.POINTER(MembersWriteIn), C.c_int, C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_int32)]
+
 lib.rgc_abi_version.restype = C.c_int
 lib.rgc_consensus.argtypes = [C.c_void_p, C.POINTER(BatchIn), C.POINTER(ConsensusOpts),
                               C.POINTER(ConsensusOut)]
@@ -151,7 +188,7 @@ EXPORTS = ["rgc_abi_version", "rgc_last_error", "rgc_device_count", "rgc_ctx_cre
            "rgc_parsed_free", "rgc_py_hash_node", "rgc_py_set_order", "rgc_test_epilogue",
            "rgc_score_pairs", "rgc_score_sweep", "rgc_score_match", "rgc_score_match_sweep", "rgc_test_iou_edge", "rgc_ilp_solve", "rgc_write_outputs", "rgc_pickle_bytes",
            "rgc_py_float_repr", "rgc_consensus", "rgc_pick_select", "rgc_write_boxes",
-           "rgc_np_float_str", "rgc_test_ji_cutoff"]
+           "rgc_np_float_str", "rgc_test_ji_cutoff", *MEMBERS_SYMBOLS]
 
 
 class RGCError(RuntimeError):
@@ -420,11 +457,13 @@ class Context:
 
     def consensus(self, n_mg, k, box_size, box_off, id_base, x, y, score, flags=0,
                   dev_meta=None, node_limit=0, num_particles=None, timing=False,
-                  ji_threshold=None):
+                  ji_threshold=None, members=False):
         """get_cliques + run_ilp in one device pass (rgc_consensus, ABI 10): ``run``'s
         arguments, then the solver's ``node_limit`` and run_ilp's ``num_particles`` (None:
         all).  The per-clique arrays stay in HBM unless ``flags`` has ``F_HOST_OUTPUTS``.
-        ``ji_threshold`` as for ``run``.
+        ``ji_threshold`` as for ``run``.  ``members``: rgc_consensus_members instead, the run
+        with ``F_MEMBERS``; the result also has ``pmx``, ``pmy``, ``left_off``, ``left_x``,
+        ``left_y`` and ``in_clique``.
         Returns a :class:`ConsensusResult` (plain copies of the pick arrays)."""
         bi, keep, flags = self._batch_in(n_mg, k, box_size, box_off, id_base, x, y, score, flags,
                                          dev_meta, ji_threshold)
@@ -432,9 +471,55 @@ class Context:
         opts = ConsensusOpts(int(node_limit), -1 if num_particles is None else int(num_particles),
                              F_TIMING if timing else 0)
         co = ConsensusOut()
-        _check(lib.rgc_consensus(self._p, C.byref(bi), C.byref(opts), C.byref(co)))
+        mo = None
+        if members:
+            _need_members()
+            mo = MembersOut()
+            flags |= F_MEMBERS
+            _check(lib.rgc_consensus_members(self._p, C.byref(bi), C.byref(opts), C.byref(co),
+                                             C.byref(mo)))
+        else:
+            _check(lib.rgc_consensus(self._p, C.byref(bi), C.byref(opts), C.byref(co)))
         del keep
-        return ConsensusResult(co, self._result(co.run, n_mg, k, flags), n_mg)
+        return ConsensusResult(co, self._result(co.run, n_mg, k, flags), n_mg, mo, k)
+
+    def pick_members(self, k, col_off, x, conf, cons, members, box_off, bx, by,
+                     num_particles=None):
+        """Test hook of the members kernels (rgc_pick_members): ``pick_select`` on columns whose
+        consensus coordinates are those of box ``cons[c]``, then the members of every written
+        pick and each (micrograph, picker) segment's leftovers -> (pick_off, px, py, pconf,
+        pcol, pmx, pmy, left_off, left_x, left_y, in_clique) copies; ``pmx`` / ``pmy`` are
+        [n_picked, k]."""
+        _need_members()
+        col_off = np.ascontiguousarray(col_off, np.int64)
+        box_off = np.ascontiguousarray(box_off, np.int64)
+        x = np.ascontiguousarray(x, np.uint8)
+        conf = np.ascontiguousarray(conf, np.float32)
+        cons = np.ascontiguousarray(cons, np.int32)
+        members = np.ascontiguousarray(members, np.int32)
+        bx = np.ascontiguousarray(bx, np.float64)
+        by = np.ascontiguousarray(by, np.float64)
+        n_mg = len(col_off) - 1
+        nc = int(col_off[-1]) if n_mg >= 0 else 0
+        assert n_mg >= 0 and len(x) == len(conf) == len(cons) == nc and members.size == nc * k
+        assert len(box_off) == n_mg * k + 1 and len(bx) == len(by) >= int(box_off[-1])
+        pi = PickMembersIn(n_mg, int(k), col_off.ctypes.data, x.ctypes.data, conf.ctypes.data,
+                           cons.ctypes.data, members.ctypes.data, box_off.ctypes.data,
+                           bx.ctypes.data, by.ctypes.data,
+                           -1 if num_particles is None else int(num_particles))
+        po, mo = PickOut(), MembersOut()
+        self._retire()
+        _check(lib.rgc_pick_members(self._p, C.byref(pi), C.byref(po), C.byref(mo)))
+        n = int(po.n_picked)
+        S = n_mg * k
+        left_off = _copy(mo.left_off, S + 1, np.int64)
+        L = int(left_off[-1])
+        return (_copy(po.pick_off, n_mg + 1, np.int64), _copy(po.px, n, np.float64),
+                _copy(po.py, n, np.float64), _copy(po.pconf, n, np.float32),
+                _copy(po.pcol, n, np.int32), _copy(mo.pmx, n * k, np.float64).reshape(n, k),
+                _copy(mo.pmy, n * k, np.float64).reshape(n, k), left_off,
+                _copy(mo.left_x, L, np.float64), _copy(mo.left_y, L, np.float64),
+                _copy(mo.in_clique, S, np.int32))
 
     def pick_select(self, col_off, x, conf, cx, cy, num_particles=None):
         """Test hook of the emit kernels (rgc_pick_select): per micrograph (columns
@@ -492,7 +577,7 @@ class ConsensusResult:
     columns before ``num_particles``; ``ilp_status`` / ``ilp_gap`` are the micrograph's
     certification (repic_amd.ilp.mg_status) and relative gap."""
 
-    def __init__(self, co: ConsensusOut, run, n_mg):
+    def __init__(self, co: ConsensusOut, run, n_mg, mo=None, k=0):
         self.run = run
         self.n_picked = int(co.n_picked)
         self.pick_off = (_copy(co.pick_off, n_mg + 1, np.int64) if n_mg
@@ -505,6 +590,18 @@ class ConsensusResult:
         self.ilp_status = _copy(co.ilp_status, n_mg, np.int32)
         self.ilp_gap = _copy(co.ilp_gap, n_mg, np.float64)
         self.h2d_bytes, self.d2h_bytes = int(co.h2d_bytes), int(co.d2h_bytes)
+        # with members=True: members of pick i (pmx[i, p]), leftovers of segment s = m k + p
+        # (left_off[s]:left_off[s+1] of left_x / left_y) and its boxes in some clique
+        self.pmx = self.pmy = self.left_off = self.left_x = self.left_y = self.in_clique = None
+        if mo is not None:
+            S = n_mg * k
+            self.pmx = _copy(mo.pmx, self.n_picked * k, np.float64).reshape(self.n_picked, k)
+            self.pmy = _copy(mo.pmy, self.n_picked * k, np.float64).reshape(self.n_picked, k)
+            self.left_off = _copy(mo.left_off, S + 1, np.int64)
+            L = int(self.left_off[-1])
+            self.left_x = _copy(mo.left_x, L, np.float64)
+            self.left_y = _copy(mo.left_y, L, np.float64)
+            self.in_clique = _copy(mo.in_clique, S, np.int32)
 
 
 def write_boxes(out_dir, bases, box_size, pick_off, count, px, py, pconf, n_threads=1):
@@ -523,6 +620,40 @@ def write_boxes(out_dir, bases, box_size, pick_off, count, px, py, pconf, n_thre
         b = bases[bad.value] if 0 <= bad.value < n else ""
         raise OSError(-rc, os.strerror(-rc) if rc < -1 else "rgc_write_boxes failed",
                       os.path.join(out_dir, b + ".box"))
+
+
+def write_members(out_dir, bases, box_size, pick_off, count, px, py, pconf, methods, pmx, pmy,
+                  seg, left_off, left_x, left_y, n_threads=1):
+    """``write_boxes`` and, from the same task per micrograph, ``<base>_members.tsv``
+    (rgc_write_members): ``methods`` are the k header names, ``pmx`` / ``pmy`` [n, k] the
+    members of pick i, ``seg[m]`` micrograph m's first segment in ``left_off``.  A skipped
+    micrograph (count -1) gets its empty ``.box`` only."""
+    _need_members()
+    n, k = len(bases), len(methods)
+    arrs = [np.ascontiguousarray(pick_off, np.int64), np.ascontiguousarray(count, np.int64),
+            np.ascontiguousarray(px, np.float64), np.ascontiguousarray(py, np.float64),
+            np.ascontiguousarray(pconf, np.float32)]
+    more = [np.ascontiguousarray(pmx, np.float64), np.ascontiguousarray(pmy, np.float64),
+            np.ascontiguousarray(seg, np.int64), np.ascontiguousarray(left_off, np.int64),
+            np.ascontiguousarray(left_x, np.float64), np.ascontiguousarray(left_y, np.float64)]
+    assert len(arrs[0]) >= n and len(arrs[1]) == n and len(more[2]) == n and k >= 1
+    assert more[0].size == more[1].size == len(arrs[2]) * k
+    bs = (C.c_char_p * max(1, n))(*[os.fsencode(b) for b in bases])
+    wi = MembersWriteIn(BoxWriteIn(os.fsencode(out_dir), n, int(box_size), bs,
+                                   *[a.ctypes.data for a in arrs]),
+                        k, os.fsencode("\t".join(methods)), *[a.ctypes.data for a in more])
+    bad, which = C.c_int64(-1), C.c_int32(0)
+    rc = lib.rgc_write_members(C.byref(wi), int(n_threads), C.byref(bad), C.byref(which))
+    if rc != 0:
+        b = bases[bad.value] if 0 <= bad.value < n else ""
+        raise OSError(-rc, os.strerror(-rc) if rc < -1 else "rgc_write_members failed",
+                      os.path.join(out_dir, b + (MEMBERS_SUFFIX if which.value else ".box")))
+
+
+def _need_members():
+    if not has_members():
+        raise RGCError(f"{LIB_PATH} has no consensus --members entry points "
+                       f"({', '.join(MEMBERS_SYMBOLS)}): rebuild it")
 
 
 def np_float_str(v) -> str:

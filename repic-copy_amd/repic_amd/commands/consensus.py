@@ -21,7 +21,11 @@ raise (parse crash, no edges -> ValueError, no cliques -> UnboundLocalError) eve
 micrograph's ``.box`` exists and the same exception class is raised; an ok micrograph whose
 packing is empty raises ``run_ilp``'s AssertionError; NODE_LIMIT / HEURISTIC micrographs get
 ``run_ilp``'s warnings on stderr.  There is no ``--multi_out`` (the reference's ``run_ilp``
-raises on such inputs) and no multi-rank form yet: with ``WORLD_SIZE > 1`` the command raises
+raises on such inputs); ``--members`` gives what that path was meant to: next to each
+``<base>.box`` a ``<base>_members.tsv`` whose row i holds, picker by picker, the boxes that
+made up ``.box`` line i, followed by every picker's boxes that are in no written pick
+(``rgc_consensus_members`` / ``rgc_write_members``), and one ``consensus_pickers.tsv`` for the
+run.  Without the flag nothing changes.  There is no multi-rank form yet: with ``WORLD_SIZE > 1`` the command raises
 before it creates a device context or touches ``out_dir``.
 """
 from __future__ import annotations
@@ -43,6 +47,9 @@ name = "consensus"
 
 SUMMARY = "consensus_summary.tsv"
 SUMMARY_HEADER = "base\tstatus\tcliques\tpicks\tcc_max\tcc_cnt\tilp_status\trel_gap\n"
+# --members: one line per ok micrograph and picker
+PICKERS = "consensus_pickers.tsv"
+PICKERS_HEADER = "base\tpicker\tboxes\tin_clique\tin_consensus\n"
 
 # phase seconds, counts and the library's host<->device byte counts of the last run in this
 # process (tools/consensus_bench.py reads them)
@@ -60,6 +67,9 @@ def add_arguments(parser):
                         help="filter for the number of expected particles (int)")
     parser.add_argument("--get_cc", action="store_true",
                         help="filters cliques for those in the largest Connected Component (CC)")
+    parser.add_argument("--members", action="store_true",
+                        help="also write <base>_members.tsv (per pick its box from every picker, "
+                             "then every picker's boxes in no pick) and consensus_pickers.tsv")
     gc.add_ji_threshold(parser)
     parser.add_argument("--node_limit", type=int, default=0,
                         help="branch-and-bound nodes per conflict component (0: the library "
@@ -103,6 +113,10 @@ def main(args):
             with open(os.path.join(args.out_dir, SUMMARY), "wt") as o:
                 o.write(SUMMARY_HEADER)
                 o.writelines(runs[0].summary)
+            if runs[0].members:
+                with open(os.path.join(args.out_dir, PICKERS), "wt") as o:
+                    o.write(PICKERS_HEADER)
+                    o.writelines(runs[0].pickers)
 
 
 class _Res:
@@ -111,12 +125,20 @@ class _Res:
     PER_MG = ("status", "cc_max", "cc_cnt", "n_vert", "n_edges_mg", "clique_cnt", "sel_cnt",
               "ilp_status", "ilp_gap")
 
-    def __init__(self, r):
+    # --members: per pick (rows of k), per segment (micrograph, picker), per leftover
+    MEMBERS = ("pmx", "pmy", "seg_boxes", "in_clique", "left_x", "left_y")
+
+    def __init__(self, r, box_off=None):
         for f in ("status", "cc_max", "cc_cnt", "n_vert", "n_edges_mg", "clique_cnt"):
             setattr(self, f, np.array(getattr(r.run, f)))
         self.sel_cnt, self.ilp_status, self.ilp_gap = r.sel_cnt, r.ilp_status, r.ilp_gap
         self.pick_off = r.pick_off
         self.px, self.py, self.pconf = r.px, r.py, r.pconf
+        self.members = r.pmx is not None
+        if self.members:
+            self.pmx, self.pmy, self.in_clique = r.pmx, r.pmy, r.in_clique
+            self.left_off, self.left_x, self.left_y = r.left_off, r.left_x, r.left_y
+            self.seg_boxes = np.diff(np.asarray(box_off, np.int64))
 
     def append(self, o):
         for f in self.PER_MG:
@@ -125,6 +147,10 @@ class _Res:
         self.px = np.concatenate([self.px, o.px])
         self.py = np.concatenate([self.py, o.py])
         self.pconf = np.concatenate([self.pconf, o.pconf])
+        if self.members:
+            for f in self.MEMBERS:
+                setattr(self, f, np.concatenate([getattr(self, f), getattr(o, f)]))
+            self.left_off = np.concatenate([self.left_off, o.left_off[1:] + self.left_off[-1]])
         return self
 
 
@@ -137,6 +163,8 @@ class _Run(gc._Run):
         self.stats.update(picks=0, h2d_bytes=0, d2h_bytes=0)
         self.summary = []
         self._empty = None
+        self.members = bool(getattr(self.args, "members", False))
+        self.pickers = []
 
     def device(self, ch):
         ch.res = None
@@ -156,10 +184,12 @@ class _Run(gc._Run):
                                    part.x, part.y, part.score, flags,
                                    node_limit=getattr(self.args, "node_limit", 0) or 0,
                                    num_particles=self.args.num_particles,
-                                   ji_threshold=self.ji)
+                                   ji_threshold=self.ji, **({"members": True} if self.members
+                                                            else {}))
             self.stats["h2d_bytes"] += r.h2d_bytes
             self.stats["d2h_bytes"] += r.d2h_bytes
-            ch.res = _Res(r) if ch.res is None else ch.res.append(_Res(r))
+            res = _Res(r, part.box_off) if self.members else _Res(r)
+            ch.res = res if ch.res is None else ch.res.append(res)
         self.stats["device_s"] += time.time() - t0
         ok = ch.res.status == _lib.OK
         self.stats["edges"] += int(ch.res.n_edges_mg[ok].sum())
@@ -169,21 +199,29 @@ class _Run(gc._Run):
         mgs = ch.mgs if stop is None else ch.mgs[:stop]
         t0 = time.time()
         r = ch.res
-        bases, offs, counts = [], [], []
+        bases, offs, counts, segs = [], [], [], []
         raise_at = None
+        k = self.k
 
         def flush():
             if bases:
+                more = {}
+                if self.members:
+                    more["members"] = (list(self.methods),) + tuple(
+                        getattr(r, f) if r is not None else None
+                        for f in ("pmx", "pmy")) + (list(segs),) + tuple(
+                        getattr(r, f) if r is not None else None
+                        for f in ("left_off", "left_x", "left_y"))
                 writer.boxes(self.args.out_dir, list(bases), self.args.box_size, list(offs),
                              list(counts), r.px if r is not None else None,
                              r.py if r is not None else None,
-                             r.pconf if r is not None else None)
-                bases.clear(), offs.clear(), counts.clear()
+                             r.pconf if r is not None else None, **more)
+                bases.clear(), offs.clear(), counts.clear(), segs.clear()
         for mg in mgs:
             print(f"\n--- {mg.base} ---\n")
             if mg.status == "skip":
                 print("Skipping micrograph - not all methods have picked particles...")
-                bases.append(mg.base), offs.append(0), counts.append(-1)
+                bases.append(mg.base), offs.append(0), counts.append(-1), segs.append(0)
                 self.summary.append(f"{mg.base}\tskip\t0\t0\t0\t0\t-\t-\n")
             elif mg.status == "crash" or r.status[mg.slot] != _lib.OK:
                 raise_at = mg
@@ -205,6 +243,11 @@ class _Run(gc._Run):
                     break
                 n = int(r.pick_off[s + 1] - r.pick_off[s])
                 bases.append(mg.base), offs.append(int(r.pick_off[s])), counts.append(n)
+                segs.append(s * k)
+                if self.members:
+                    self.pickers.extend(
+                        f"{mg.base}\t{self.methods[p]}\t{int(r.seg_boxes[s * k + p])}\t"
+                        f"{int(r.in_clique[s * k + p])}\t{n}\n" for p in range(k))
                 self.summary.append(
                     f"{mg.base}\tok\t{int(r.clique_cnt[s])}\t{n}\t{int(r.cc_max[s])}\t"
                     f"{int(r.cc_cnt[s])}\t{STATUS_NAMES[st]}\t{float(r.ilp_gap[s]):.3e}\n")

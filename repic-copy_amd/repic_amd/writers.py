@@ -249,6 +249,33 @@ OK_FILES = ("_weight_vector.pickle", "_consensus_coords.pickle",
             "_consensus_confidences.pickle", "_constraint_matrix.pickle", "_runtime.tsv")
 
 
+# ... and of `repic consensus --members` for a micrograph that is not skipped
+MEMBERS_FILES = (".box", "_members.tsv")
+
+
+def read_members(path):
+    """``<base>_members.tsv`` -> (coords, labels, weights): ``labels`` the k picker names of
+    the header, ``coords[i][p]`` the ``(x, y)`` floats of row i's box from picker p or ``()``
+    where the row has ``N/A``, ``weights[i]`` the row's last field as a float."""
+    with open(path, "rt") as f:
+        text = f.read()
+    head, _, body = text.partition("\n")
+    labels = head.split("\t")
+    k = len(labels)
+    coords, weights = [], []
+    for ln in body.split("\n") if body else []:
+        fields = ln.split("\t")
+        if len(fields) != 2 * k + 1:
+            raise ValueError(f"{path}: a row of {len(fields)} fields under {k} labels")
+        row = []
+        for p in range(k):
+            fx, fy = fields[2 * p], fields[2 * p + 1]
+            row.append(() if fx == "N/A" and fy == "N/A" else (float(fx), float(fy)))
+        coords.append(row)
+        weights.append(float(fields[-1]))
+    return coords, labels, weights
+
+
 class BoxWriter:
     """Pooled writer of ``repic consensus``: groups of final ``<base>.box`` files through the
     library's ``rgc_write_boxes`` (C++ formatting and file creation without the GIL) on a few
@@ -264,22 +291,36 @@ class BoxWriter:
         self._bases = set()
         self.written = []
 
-    def boxes(self, out_dir, bases, box_size, pick_off, count, px, py, pconf):
+    def boxes(self, out_dir, bases, box_size, pick_off, count, px, py, pconf, members=None):
         """One task: ``<base>.box`` of each micrograph, picks ``pick_off[m] : + count[m]`` of
-        the pick arrays (count -1: the empty file of a skipped micrograph)."""
+        the pick arrays (count -1: the empty file of a skipped micrograph).  ``members`` =
+        (methods, pmx, pmy, seg, left_off, left_x, left_y) as for ``_lib.write_members``: the
+        same task also writes ``<base>_members.tsv`` of every micrograph that is not skipped."""
         from . import _lib
         if any(b in self._bases for b in bases):   # same name twice: the reference's order
             self._drain()
         self._bases.update(bases)
-        self.written.extend((b, SKIP_FILES) for b in bases)
+        if members is None:
+            self.written.extend((b, SKIP_FILES) for b in bases)
+        else:
+            self.written.extend((b, SKIP_FILES if n < 0 else MEMBERS_FILES)
+                                for b, n in zip(bases, count))
         if px is None:
             px = py = np.zeros(0, np.float64)
             pconf = np.zeros(0, np.float32)
         args = (out_dir, bases, box_size, pick_off, count, px, py, pconf)
+        fn = _lib.write_boxes
+        if members is not None:
+            methods, pmx, pmy, seg, left_off, left_x, left_y = members
+            if pmx is None:   # (a chunk without a device batch: skipped micrographs only)
+                pmx = pmy = np.zeros((0, len(methods)), np.float64)
+                left_off, left_x, left_y = np.zeros(1, np.int64), px[:0], px[:0]
+            args += (methods, pmx, pmy, seg, left_off, left_x, left_y)
+            fn = _lib.write_members
         if self._pool is None:
-            _lib.write_boxes(*args)
+            fn(*args)
             return
-        self._futs.append(self._pool.submit(_lib.write_boxes, *args))
+        self._futs.append(self._pool.submit(fn, *args))
         if len(self._futs) > 4 * self.threads:
             self._drain(len(self._futs) // 2)
 

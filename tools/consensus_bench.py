@@ -12,6 +12,10 @@ its own ``timeout -k 10``, one at a time, and the chain stops at the first non-z
 A run's time is the wall time of its child processes (interpreter start and imports included:
 what a user of the CLI waits for).  The ``.box`` files of (a) and (b) must be byte-identical.
 ``--baseline-root`` runs (a) from another checkout (e.g. the parent commit, built there).
+``--members`` measures ``consensus --members`` instead: per repeat, interleaved, (a) plain
+consensus from ``--baseline-root`` (the parent commit, built there; this checkout without it),
+(b) plain consensus from this checkout and (c) ``consensus --members`` from this checkout; the
+``.box`` files of all three must be byte-identical.
 Prints one JSON line.
 """
 from __future__ import annotations
@@ -43,6 +47,8 @@ def _child(a):
         ns = argparse.Namespace(in_dir=a.in_dir, out_dir=a.out_dir, box_size=a.box,
                                 multi_out=False, get_cc=False, batch_boxes=1 << 25, threads=None,
                                 device=None, listing=None, num_particles=None, node_limit=0)
+        if a.with_members:
+            ns.members = True
     with open(os.devnull, "w") as null:
         so, sys.stdout = sys.stdout, null     # the per-micrograph banner lines
         try:
@@ -57,14 +63,14 @@ def _child(a):
         json.dump(res, f)
 
 
-def _run_child(cmd, root, in_dir, out_dir, box, limit, work):
+def _run_child(cmd, root, in_dir, out_dir, box, limit, work, members=False):
     """-> (wall seconds, the child's phase dict); raises on a non-zero exit."""
     result = os.path.join(work, f"res_{cmd}.json")
     if os.path.exists(result):
         os.remove(result)
     argv = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__),
             "--child", cmd, "--root", root, "--in_dir", in_dir, "--out_dir", out_dir,
-            "--box", str(box), "--result", result]
+            "--box", str(box), "--result", result] + (["--with_members"] if members else [])
     t0 = time.perf_counter()
     r = subprocess.run(argv, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
     wall = time.perf_counter() - t0
@@ -97,9 +103,14 @@ def main():
     for n in ("--root", "--in_dir", "--out_dir", "--result"):
         ap.add_argument(n, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--box", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--with_members", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--members", action="store_true",
+                    help="time consensus --members against plain consensus (see above)")
     a = ap.parse_args()
     if a.child:
         return _child(a)
+    if a.members:
+        return _members(a)
 
     sys.path.insert(0, os.path.join(ROOT, "repic-copy_amd"))
     from repic_amd import synth
@@ -151,6 +162,53 @@ def main():
         c = ph_c[-1]
         out["cliques"], out["picks"] = c.get("cliques"), c.get("picks")
         out["h2d_bytes"], out["d2h_bytes"] = c.get("h2d_bytes"), c.get("d2h_bytes")
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+    print(json.dumps(out))
+
+
+def _members(a):
+    """--members: baseline consensus | consensus | consensus --members, interleaved."""
+    sys.path.insert(0, os.path.join(ROOT, "repic-copy_amd"))
+    from repic_amd import synth
+    cfg = synth.SynthConfig(**synth.CONFIGS[a.config], seed=0)
+    base_root = os.path.abspath(a.baseline_root) if a.baseline_root else ROOT
+    work = tempfile.mkdtemp(prefix="rgc_cons_", dir=a.workdir)
+    out = {"metric": "file-to-file seconds, BOX directories -> final .box files (1 GPU)",
+           "config": a.config, "n_mg": a.n_mg, "k": cfg.k, "repeats": a.repeats,
+           "baseline": "other checkout" if a.baseline_root else "this checkout"}
+    arms = (("baseline_consensus", base_root, False), ("consensus", ROOT, False),
+            ("consensus_members", ROOT, True))
+    try:
+        in_dir = os.path.join(work, "in")
+        synth.write_box_dirs(in_dir, cfg, a.n_mg)
+        secs = {n: [] for n, _, _ in arms}
+        last = {}
+        for i in range(a.repeats):
+            want = None
+            for n, root, mem in arms:
+                d = os.path.join(work, f"{n}_{i}")
+                t, ph = _run_child("consensus", root, in_dir, d, cfg.box, a.timeout, work, mem)
+                secs[n].append(t)
+                last[n] = ph
+                got = _boxes(d)
+                assert want is None or got == want, f"{n}: .box files differ from the baseline's"
+                want = got
+                out["files_" + n] = len(os.listdir(d))
+                shutil.rmtree(d)
+        out["box_files"] = len(want)
+        out["box_files_identical"] = True
+        for n, _, _ in arms:
+            out[n + "_s"] = secs[n]
+            out[n + "_median_s"] = statistics.median(secs[n])
+            out[n + "_range_s"] = [min(secs[n]), max(secs[n])]
+            out[n + "_h2d_bytes"] = last[n].get("h2d_bytes")
+            out[n + "_d2h_bytes"] = last[n].get("d2h_bytes")
+            out[n + "_device_s"] = last[n].get("device_s")
+            out[n + "_write_s"] = last[n].get("write_s")
+        lo, hi = out["baseline_consensus_range_s"]
+        out["plain_median_inside_baseline_range"] = lo <= out["consensus_median_s"] <= hi
+        out["cliques"], out["picks"] = last["consensus"].get("cliques"), last["consensus"].get("picks")
     finally:
         shutil.rmtree(work, ignore_errors=True)
     print(json.dumps(out))
