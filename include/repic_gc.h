@@ -154,7 +154,7 @@ int rgc_run(rgc_ctx* ctx, const rgc_batch_in* in, rgc_batch_out* out);
  * host once per clique level, so a second context on its own stream keeps the device busy
  * meanwhile), and one whose micrographs need a second pass re-runs that path inside rgc_wait.
  * Outputs stay valid until the next submit/run on the same context.  While a submitted
- * run awaits rgc_wait, rgc_submit, rgc_run, rgc_score_pairs, rgc_score_sweep, rgc_score_match, rgc_score_match_sweep and rgc_ilp_solve on the same
+ * run awaits rgc_wait, rgc_submit, rgc_run, rgc_score_pairs, rgc_score_sweep, rgc_score_match, rgc_score_match_sweep, rgc_nms and rgc_ilp_solve on the same
  * context fail (negative return, rgc_last_error says why). */
 int rgc_submit(rgc_ctx* ctx, const rgc_batch_in* in);
 int rgc_wait(rgc_ctx* ctx, rgc_batch_out* out);
@@ -264,6 +264,38 @@ int rgc_score_match_sweep(rgc_ctx* ctx, const rgc_score_match_sweep_in* in,
                           int64_t* counts /* [n_pairs][T][3] */);
 /* Host twin of the device edge test of rgc_score_match on two boxes (x0, x1, y0, y1): 1 / 0. */
 int rgc_test_iou_edge(const int32_t a[4], const int32_t b[4], double t);
+
+/* Greedy non-maximum suppression (beyond the reference).  A segment is a list of boxes in
+ * priority order (index 0 is the highest priority); all boxes are squares of side box_size with
+ * lower-left corner (x, y) in f64.  Two boxes conflict iff the reference quotient exceeds the
+ * threshold: calc_jaccard of get_cliques.py:40-46 in its f64 operation order (no FMA, one
+ * division), strict `> ji_threshold`.  keep[i] = 1 iff no j < i of the same segment has
+ * keep[j] = 1 and conflicts with i.  That set is unique (it is the greedy result, and the only
+ * set for which the sentence holds at every i), so the output is a function of the input alone.
+ * A box with a non-finite coordinate conflicts with nothing (the formula yields 0 or NaN there):
+ * it is kept and suppresses nothing.  Boxes of different segments never interact.  kept[s] = the
+ * boxes kept of segment s.  n_seg == 0 and empty segments are valid and launch nothing.
+ * One workgroup per segment decides its boxes in rounds, at most n + 1 for n boxes; a segment
+ * that ran out of rounds fails the call.  RGC_F_TIMING records "k_nms_count" and "k_nms".
+ * Refused before any launch, the context staying usable: null arguments with boxes to read or
+ * write, a submitted run awaiting rgc_wait, n_seg outside 0..INT32_MAX, offsets that do not
+ * start at 0 or decrease, more than 2^31 - 1 boxes, box_size outside 1..2^26, a threshold that is
+ * NaN or outside [0, 1); refused after the count launch: more than 2^31 - 1 conflict edges.
+ * Additive symbols: no struct changes layout and RGC_ABI_VERSION stays 11; a caller finds out
+ * whether the library has them by looking the symbols up. */
+typedef struct rgc_nms_in {
+  int64_t n_seg;
+  const int64_t* seg_off;   /* HOST [n_seg + 1], starts at 0, non-decreasing */
+  const double* x;          /* HOST [n] lower-left x, each segment in priority order */
+  const double* y;
+  int64_t box_size;         /* 1..2^26 */
+  double ji_threshold;      /* finite, 0 <= t < 1 */
+  uint32_t flags;           /* RGC_F_TIMING */
+} rgc_nms_in;
+int rgc_nms(rgc_ctx* ctx, const rgc_nms_in* in, uint8_t* keep /* [n] */,
+            int64_t* kept /* [n_seg] */);
+/* Bytes the last rgc_nms on ctx copied to and from the device (0, 0 when it launched nothing). */
+int rgc_nms_last_bytes(rgc_ctx* ctx, int64_t* h2d, int64_t* d2h);
 
 /* run_ilp (repic/commands/run_ilp.py:50-63): maximise w.x over binary x subject to A x <= 1,
  * exactly, for a batch of micrographs at once (rows are global box ids: micrographs never

@@ -70,6 +70,10 @@ enum DevBufId {
   // uploaded cons / members
   D_PM_META, D_PM_INPICK, D_PM_INCL, D_PM_X, D_PM_Y, D_PM_LX, D_PM_LY, D_PM_SEG, D_PM_CONS,
   D_PM_MEMB,
+  // greedy NMS (rgc_nms.hip): layout, coordinates in priority and in x order, per-box state,
+  // per-segment edges and results
+  D_NM_OFF, D_NM_NS, D_NM_XY, D_NM_SXY, D_NM_SIDX, D_NM_STATE, D_NM_ETOT, D_NM_EBASE, D_NM_ADJ,
+  D_NM_KEEP, D_NM_KEPT, D_NM_STAT,
   D_COUNT
 };
 enum HostBufId {
@@ -134,6 +138,7 @@ struct rgc_ctx {
   std::thread worker;
   std::string pend_err;          // the worker's error message (g_err is per thread)
   int64_t fix_fetch_bytes = 0;   // rgc_consensus: CSC bytes fetched for reduced-cost fixing
+  int64_t nms_h2d = 0, nms_d2h = 0;   // rgc_nms: bytes the last call copied (rgc_nms_last_bytes)
 };
 
 // ---- arena, events (rgc_ctx.cpp)

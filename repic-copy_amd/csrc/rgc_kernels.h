@@ -395,6 +395,34 @@ void launch_match(hipStream_t stream, int n_pairs, const MatchArgs& A);
 void launch_match_sweep(hipStream_t stream, int n_pairs, const MatchArgs& A, int n_thr,
                         const int64_t* keep, int64_t* tp_out);
 
+// greedy non-maximum suppression (rgc_nms.hip): one workgroup per segment.  Segment p's boxes
+// are [off[p], off[p + 1]) of x / y, in priority order; every per-box array below is indexed like
+// them.  sx / sy / sidx hold, in the first ns[p] slots of the segment's range, its boxes with
+// finite coordinates in ascending x and their index within the segment.
+struct NmsArgs {
+  const int64_t* off;         // [n_seg + 1]
+  const int32_t* ns;          // [n_seg] boxes of the segment with finite coordinates
+  const double* x;
+  const double* y;
+  const double* sx;
+  const double* sy;
+  const int32_t* sidx;
+  double B, two_b2, t;        // conflict <=> jaccard(..., B, two_b2) > t
+  int32_t* cnt;               // conflicting neighbours of higher priority (k_nms_count)
+  int32_t* rowp;              // first of them in adj, relative to ebase[p]
+  int32_t* state;             // 0 undecided, 1 kept, 2 suppressed
+  int64_t* etot;              // [n_seg] sum of cnt over the segment (k_nms_count)
+  const int64_t* ebase;       // [n_seg] the host's scan of etot
+  int32_t* adj;               // [edges] index within the segment
+  uint8_t* keep;              // the result
+  int64_t* kept;              // [n_seg] boxes kept
+  int32_t* status;            // [n_seg] 0, or NMS_ST_*
+};
+constexpr int NMS_ST_ROUNDS = 1;     // more rounds than the segment's boxes + 1
+constexpr int NMS_ST_LIST = 2;       // a conflict list names a box that is not of higher priority
+void launch_nms_count(hipStream_t stream, int n_seg, const NmsArgs& A);
+void launch_nms(hipStream_t stream, int n_seg, const NmsArgs& A);
+
 // run_ilp exact set packing (rgc_ilp.hip)
 struct IlpArgs {
   int64_t n_cols, n_rows, n_comp;

@@ -142,6 +142,25 @@ if has_members():
     lib.rgc_write_members.argtypes = [C.POINTER(MembersWriteIn), C.c_int, C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int32)]
 
+class NmsIn(C.Structure):
+    _fields_ = [("n_seg", C.c_int64), ("seg_off", C.c_void_p), ("x", C.c_void_p),
+                ("y", C.c_void_p), ("box_size", C.c_int64), ("ji_threshold", C.c_double),
+                ("flags", C.c_uint32)]
+
+
+NMS_SYMBOLS = ("rgc_nms", "rgc_nms_last_bytes")
+
+
+def has_nms() -> bool:
+    """The loaded library has the greedy-NMS entry points (additive symbols: the ABI version
+    does not tell)."""
+    return all(hasattr(lib, n) for n in NMS_SYMBOLS)
+
+
+if has_nms():
+    lib.rgc_nms.argtypes = [C.c_void_p, C.POINTER(NmsIn), C.c_void_p, C.c_void_p]
+    lib.rgc_nms_last_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+
 lib.rgc_abi_version.restype = C.c_int
 lib.rgc_consensus.argtypes = [C.c_void_p, C.POINTER(BatchIn), C.POINTER(ConsensusOpts),
                               C.POINTER(ConsensusOut)]
@@ -188,7 +207,7 @@ EXPORTS = ["rgc_abi_version", "rgc_last_error", "rgc_device_count", "rgc_ctx_cre
            "rgc_parsed_free", "rgc_py_hash_node", "rgc_py_set_order", "rgc_test_epilogue",
            "rgc_score_pairs", "rgc_score_sweep", "rgc_score_match", "rgc_score_match_sweep", "rgc_test_iou_edge", "rgc_ilp_solve", "rgc_write_outputs", "rgc_pickle_bytes",
            "rgc_py_float_repr", "rgc_consensus", "rgc_pick_select", "rgc_write_boxes",
-           "rgc_np_float_str", "rgc_test_ji_cutoff", *MEMBERS_SYMBOLS]
+           "rgc_np_float_str", "rgc_test_ji_cutoff", *MEMBERS_SYMBOLS, *NMS_SYMBOLS]
 
 
 class RGCError(RuntimeError):
@@ -543,6 +562,31 @@ class Context:
                 _copy(po.py, n, np.float64), _copy(po.pconf, n, np.float32),
                 _copy(po.pcol, n, np.int32))
 
+    def nms(self, seg_off, x, y, box_size, ji_threshold, timing=False):
+        """Greedy non-maximum suppression (rgc_nms): segment s holds the boxes
+        ``seg_off[s]:seg_off[s+1]`` of ``x`` / ``y`` (lower-left corners of squares of side
+        ``box_size``) in priority order; a box is kept iff no kept box before it in its segment
+        has a Jaccard index with it above ``ji_threshold`` (the reference's f64 quotient, strict).
+        -> (keep uint8[n], kept int64[n_seg]).  ``nms_bytes`` then holds the (H2D, D2H) bytes
+        the call copied.  The context's host buffers are not touched: a Result stays valid."""
+        _need_nms()
+        seg_off = np.ascontiguousarray(seg_off, np.int64)
+        x = np.ascontiguousarray(x, np.float64)
+        y = np.ascontiguousarray(y, np.float64)
+        n_seg = len(seg_off) - 1
+        assert seg_off.ndim == 1 and n_seg >= 0
+        n = int(seg_off[-1])
+        assert x.shape == y.shape == (n,)
+        keep = np.zeros(n, np.uint8)
+        kept = np.zeros(n_seg, np.int64)
+        ni = NmsIn(n_seg, seg_off.ctypes.data, x.ctypes.data, y.ctypes.data, int(box_size),
+                   float(ji_threshold), F_TIMING if timing else 0)
+        _check(lib.rgc_nms(self._p, C.byref(ni), keep.ctypes.data, kept.ctypes.data))
+        h2d, d2h = C.c_int64(0), C.c_int64(0)
+        _check(lib.rgc_nms_last_bytes(self._p, C.byref(h2d), C.byref(d2h)))
+        self.nms_bytes = (h2d.value, d2h.value)
+        return keep, kept
+
     def last_edges(self):
         """Test hook: (u, v, ji) copies of the JI > threshold edges of the last run with F_EDGES
         (batch box indices; order unspecified)."""
@@ -654,6 +698,12 @@ def _need_members():
     if not has_members():
         raise RGCError(f"{LIB_PATH} has no consensus --members entry points "
                        f"({', '.join(MEMBERS_SYMBOLS)}): rebuild it")
+
+
+def _need_nms():
+    if not has_nms():
+        raise RGCError(f"{LIB_PATH} has no greedy-NMS entry points "
+                       f"({', '.join(NMS_SYMBOLS)}): rebuild it")
 
 
 def np_float_str(v) -> str:

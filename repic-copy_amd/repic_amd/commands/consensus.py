@@ -25,7 +25,20 @@ raises on such inputs); ``--members`` gives what that path was meant to: next to
 ``<base>.box`` a ``<base>_members.tsv`` whose row i holds, picker by picker, the boxes that
 made up ``.box`` line i, followed by every picker's boxes that are in no written pick
 (``rgc_consensus_members`` / ``rgc_write_members``), and one ``consensus_pickers.tsv`` for the
-run.  Without the flag nothing changes.  There is no multi-rank form yet: with ``WORLD_SIZE > 1`` the command raises
+run.  Without the flag nothing changes.
+
+``--dedup_ji T`` applies the consensus rule to the written picks themselves: the set packing
+makes the chosen cliques vertex-disjoint, which does not keep two of them from sitting on the
+same particle.  Each micrograph's lines, in their written order (confidence descending, which is
+the priority order) and with the rounded coordinates that go into the file, are one segment of a
+greedy non-maximum suppression on the device (``rgc_nms``): a line is dropped iff a line kept
+before it has a Jaccard index with it above T, so no two lines of a written ``.box`` have
+JI > T.  With ``--num_particles N`` the device returns all picks, the suppression runs, and the
+first N survivors are written.  ``consensus_dedup.tsv`` (one row per ok micrograph) counts what
+was picked, suppressed and written.  ``--dedup_ji`` with ``--members`` is refused (the members of
+a suppressed pick would have to become leftovers, which is not defined yet).
+
+There is no multi-rank form yet: with ``WORLD_SIZE > 1`` the command raises
 before it creates a device context or touches ``out_dir``.
 """
 from __future__ import annotations
@@ -50,6 +63,9 @@ SUMMARY_HEADER = "base\tstatus\tcliques\tpicks\tcc_max\tcc_cnt\tilp_status\trel_
 # --members: one line per ok micrograph and picker
 PICKERS = "consensus_pickers.tsv"
 PICKERS_HEADER = "base\tpicker\tboxes\tin_clique\tin_consensus\n"
+# --dedup_ji: one line per ok micrograph
+DEDUP = "consensus_dedup.tsv"
+DEDUP_HEADER = "base\tpicked\tsuppressed\twritten\n"
 
 # phase seconds, counts and the library's host<->device byte counts of the last run in this
 # process (tools/consensus_bench.py reads them)
@@ -71,6 +87,10 @@ def add_arguments(parser):
                         help="also write <base>_members.tsv (per pick its box from every picker, "
                              "then every picker's boxes in no pick) and consensus_pickers.tsv")
     gc.add_ji_threshold(parser)
+    parser.add_argument("--dedup_ji", type=gc._ji_type, default=None, metavar="T",
+                        help="drop a written pick whose Jaccard index with a pick written before "
+                             "it exceeds T (float, 0 <= T < 1; default: no suppression); also "
+                             "writes consensus_dedup.tsv")
     parser.add_argument("--node_limit", type=int, default=0,
                         help="branch-and-bound nodes per conflict component (0: the library "
                              "default), as for run_ilp")
@@ -86,6 +106,12 @@ def add_arguments(parser):
 def main(args):
     assert os.path.exists(args.in_dir), "Error - input directory does not exist"
     gc.ji_threshold_of(args)   # (ValueError before a context exists or anything is deleted)
+    dedup = dedup_ji_of(args)  # (likewise)
+    if dedup is not None and getattr(args, "members", False):
+        raise _lib.RGCError(
+            "repic consensus: --dedup_ji and --members cannot be combined: the members of a "
+            "suppressed pick would have to become leftovers, which is not defined yet "
+            "(nothing was deleted or written)")
     world, rank, local = gc._dist_env()
     if world > 1:
         raise _lib.RGCError(
@@ -117,6 +143,17 @@ def main(args):
                 with open(os.path.join(args.out_dir, PICKERS), "wt") as o:
                     o.write(PICKERS_HEADER)
                     o.writelines(runs[0].pickers)
+            if runs[0].dedup is not None:
+                with open(os.path.join(args.out_dir, DEDUP), "wt") as o:
+                    o.write(DEDUP_HEADER)
+                    o.writelines(runs[0].dedup_rows)
+
+
+def dedup_ji_of(args):
+    """The run's ``--dedup_ji`` threshold, validated (ValueError outside [0, 1)), or None without
+    the option (also when a hand-built namespace lacks it)."""
+    t = getattr(args, "dedup_ji", None)
+    return None if t is None else _lib.check_ji_threshold(t)
 
 
 class _Res:
@@ -128,7 +165,11 @@ class _Res:
     # --members: per pick (rows of k), per segment (micrograph, picker), per leftover
     MEMBERS = ("pmx", "pmy", "seg_boxes", "in_clique", "left_x", "left_y")
 
-    def __init__(self, r, box_off=None):
+    def __init__(self, r, box_off=None, dedup=None):
+        # --dedup_ji: (picks the device returned, picks suppressed) per micrograph
+        self.dedup = dedup is not None
+        if self.dedup:
+            self.picked, self.suppressed = dedup
         for f in ("status", "cc_max", "cc_cnt", "n_vert", "n_edges_mg", "clique_cnt"):
             setattr(self, f, np.array(getattr(r.run, f)))
         self.sel_cnt, self.ilp_status, self.ilp_gap = r.sel_cnt, r.ilp_status, r.ilp_gap
@@ -147,6 +188,9 @@ class _Res:
         self.px = np.concatenate([self.px, o.px])
         self.py = np.concatenate([self.py, o.py])
         self.pconf = np.concatenate([self.pconf, o.pconf])
+        if self.dedup:
+            self.picked = np.concatenate([self.picked, o.picked])
+            self.suppressed = np.concatenate([self.suppressed, o.suppressed])
         if self.members:
             for f in self.MEMBERS:
                 setattr(self, f, np.concatenate([getattr(self, f), getattr(o, f)]))
@@ -165,6 +209,10 @@ class _Run(gc._Run):
         self._empty = None
         self.members = bool(getattr(self.args, "members", False))
         self.pickers = []
+        self.dedup = dedup_ji_of(self.args)
+        self.dedup_rows = []
+        if self.dedup is not None:
+            self.stats.update(suppressed=0, dedup_s=0.0, dedup_h2d_bytes=0, dedup_d2h_bytes=0)
 
     def device(self, ch):
         ch.res = None
@@ -183,17 +231,53 @@ class _Run(gc._Run):
             r = self.ctx.consensus(part.n_mg, part.k, part.box_size, part.box_off, part.id_base,
                                    part.x, part.y, part.score, flags,
                                    node_limit=getattr(self.args, "node_limit", 0) or 0,
-                                   num_particles=self.args.num_particles,
+                                   num_particles=(self.args.num_particles
+                                                  if self.dedup is None else None),
                                    ji_threshold=self.ji, **({"members": True} if self.members
                                                             else {}))
             self.stats["h2d_bytes"] += r.h2d_bytes
             self.stats["d2h_bytes"] += r.d2h_bytes
-            res = _Res(r, part.box_off) if self.members else _Res(r)
+            if self.dedup is not None:
+                res = _Res(r, dedup=self._suppress(r, part.box_size))
+            else:
+                res = _Res(r, part.box_off) if self.members else _Res(r)
             ch.res = res if ch.res is None else ch.res.append(res)
         self.stats["device_s"] += time.time() - t0
         ok = ch.res.status == _lib.OK
         self.stats["edges"] += int(ch.res.n_edges_mg[ok].sum())
         self.stats["cliques"] += int(ch.res.clique_cnt[ok].sum())
+
+    def _suppress(self, r, box_size):
+        """--dedup_ji on one consensus call's picks, in place: every micrograph's lines are one
+        NMS segment in their written order, with the coordinates that go into the file;
+        suppressed lines are dropped and, with --num_particles N, the first N survivors stay.
+        -> per micrograph (picks the device returned, picks suppressed)."""
+        t0 = time.time()
+        timing = bool(getattr(self.args, "dedup_timing", False))
+        keep, kept = self.ctx.nms(r.pick_off, r.px, r.py, box_size, self.dedup, timing=timing)
+        if timing:
+            for nm, ms in self.ctx.kernel_times():
+                self.stats[nm + "_ms"] = self.stats.get(nm + "_ms", 0.0) + ms
+        h2d, d2h = self.ctx.nms_bytes
+        for f, v in (("h2d_bytes", h2d), ("d2h_bytes", d2h), ("dedup_h2d_bytes", h2d),
+                     ("dedup_d2h_bytes", d2h)):
+            self.stats[f] += v
+        picked = np.diff(r.pick_off)
+        keep = keep.astype(bool)
+        n_par = self.args.num_particles
+        written = keep
+        if n_par is not None and n_par >= 0:
+            # rank of each survivor within its micrograph (the library's rule: < 0 keeps all)
+            before = np.concatenate([[0], np.cumsum(keep)])   # survivors before each line
+            rank = before[:-1] - np.repeat(before[r.pick_off[:-1]], picked)
+            written = keep & (rank < n_par)
+        off = np.concatenate([[0], np.cumsum(written)])[r.pick_off].astype(np.int64)
+        r.pick_off = off
+        r.px, r.py, r.pconf, r.pcol = r.px[written], r.py[written], r.pconf[written], r.pcol[written]
+        r.n_picked = int(off[-1])
+        self.stats["suppressed"] += int(picked.sum() - kept.sum())
+        self.stats["dedup_s"] += time.time() - t0
+        return picked.astype(np.int64), (picked - kept).astype(np.int64)
 
     def write(self, ch, writer, stop=None):
         mgs = ch.mgs if stop is None else ch.mgs[:stop]
@@ -248,6 +332,9 @@ class _Run(gc._Run):
                     self.pickers.extend(
                         f"{mg.base}\t{self.methods[p]}\t{int(r.seg_boxes[s * k + p])}\t"
                         f"{int(r.in_clique[s * k + p])}\t{n}\n" for p in range(k))
+                if r.dedup:
+                    self.dedup_rows.append(
+                        f"{mg.base}\t{int(r.picked[s])}\t{int(r.suppressed[s])}\t{n}\n")
                 self.summary.append(
                     f"{mg.base}\tok\t{int(r.clique_cnt[s])}\t{n}\t{int(r.cc_max[s])}\t"
                     f"{int(r.cc_cnt[s])}\t{STATUS_NAMES[st]}\t{float(r.ilp_gap[s]):.3e}\n")

@@ -16,6 +16,12 @@ what a user of the CLI waits for).  The ``.box`` files of (a) and (b) must be by
 consensus from ``--baseline-root`` (the parent commit, built there; this checkout without it),
 (b) plain consensus from this checkout and (c) ``consensus --members`` from this checkout; the
 ``.box`` files of all three must be byte-identical.
+``--dedup_ji T`` measures ``consensus --dedup_ji T`` instead: per repeat, interleaved, (a) plain
+consensus and (b) ``consensus --dedup_ji T``, both from this checkout; every ``.box`` of (b) must
+be a subsequence of (a)'s lines and the lines missing must add up to the run's ``suppressed``.
+One more run of (b), outside the medians, records the device milliseconds of ``k_nms_count`` and
+``k_nms`` (RGC_F_TIMING).  The result also goes to ``--out`` (default
+``profiles/consensus_dedup_f2f_<config>.json``).
 Prints one JSON line.
 """
 from __future__ import annotations
@@ -49,6 +55,9 @@ def _child(a):
                                 device=None, listing=None, num_particles=None, node_limit=0)
         if a.with_members:
             ns.members = True
+        if a.with_dedup is not None:
+            ns.dedup_ji = a.with_dedup
+            ns.dedup_timing = a.dedup_timing
     with open(os.devnull, "w") as null:
         so, sys.stdout = sys.stdout, null     # the per-micrograph banner lines
         try:
@@ -63,7 +72,8 @@ def _child(a):
         json.dump(res, f)
 
 
-def _run_child(cmd, root, in_dir, out_dir, box, limit, work, members=False):
+def _run_child(cmd, root, in_dir, out_dir, box, limit, work, members=False, dedup=None,
+               dedup_timing=False):
     """-> (wall seconds, the child's phase dict); raises on a non-zero exit."""
     result = os.path.join(work, f"res_{cmd}.json")
     if os.path.exists(result):
@@ -71,6 +81,8 @@ def _run_child(cmd, root, in_dir, out_dir, box, limit, work, members=False):
     argv = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__),
             "--child", cmd, "--root", root, "--in_dir", in_dir, "--out_dir", out_dir,
             "--box", str(box), "--result", result] + (["--with_members"] if members else [])
+    if dedup is not None:
+        argv += ["--with_dedup", repr(float(dedup))] + (["--dedup_timing"] if dedup_timing else [])
     t0 = time.perf_counter()
     r = subprocess.run(argv, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
     wall = time.perf_counter() - t0
@@ -106,11 +118,18 @@ def main():
     ap.add_argument("--with_members", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--members", action="store_true",
                     help="time consensus --members against plain consensus (see above)")
+    ap.add_argument("--with_dedup", type=float, default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--dedup_timing", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dedup_ji", type=float, default=None, metavar="T",
+                    help="time consensus --dedup_ji T against plain consensus (see above)")
+    ap.add_argument("--out", default=None, help="--dedup_ji: also write the JSON result here")
     a = ap.parse_args()
     if a.child:
         return _child(a)
     if a.members:
         return _members(a)
+    if a.dedup_ji is not None:
+        return _dedup(a)
 
     sys.path.insert(0, os.path.join(ROOT, "repic-copy_amd"))
     from repic_amd import synth
@@ -211,6 +230,79 @@ def _members(a):
         out["cliques"], out["picks"] = last["consensus"].get("cliques"), last["consensus"].get("picks")
     finally:
         shutil.rmtree(work, ignore_errors=True)
+    print(json.dumps(out))
+
+
+def _is_subsequence(short, full):
+    it = iter(full)
+    return all(any(ln == x for x in it) for ln in short)
+
+
+def _dedup(a):
+    """--dedup_ji T: consensus | consensus --dedup_ji T, interleaved, then one timed run."""
+    sys.path.insert(0, os.path.join(ROOT, "repic-copy_amd"))
+    from repic_amd import synth
+    cfg = synth.SynthConfig(**synth.CONFIGS[a.config], seed=0)
+    work = tempfile.mkdtemp(prefix="rgc_cons_", dir=a.workdir)
+    out = {"metric": "file-to-file seconds, BOX directories -> final .box files (1 GPU)",
+           "config": a.config, "n_mg": a.n_mg, "k": cfg.k, "repeats": a.repeats,
+           "dedup_ji": a.dedup_ji, "baseline": "plain consensus, this checkout"}
+    arms = (("consensus", None), ("consensus_dedup", a.dedup_ji))
+    try:
+        in_dir = os.path.join(work, "in")
+        synth.write_box_dirs(in_dir, cfg, a.n_mg)
+        secs = {n: [] for n, _ in arms}
+        last = {}
+        for i in range(a.repeats):
+            boxes = {}
+            for n, t in arms:
+                d = os.path.join(work, f"{n}_{i}")
+                w, ph = _run_child("consensus", ROOT, in_dir, d, cfg.box, a.timeout, work,
+                                   dedup=t)
+                secs[n].append(w)
+                last[n] = ph
+                boxes[n] = _boxes(d)
+                out["files_" + n] = len(os.listdir(d))
+                shutil.rmtree(d)
+            plain, ded = boxes["consensus"], boxes["consensus_dedup"]
+            assert sorted(plain) == sorted(ded), "--dedup_ji wrote another set of .box files"
+            gone = 0
+            for f in plain:
+                pl, dl = plain[f].splitlines(), ded[f].splitlines()
+                assert _is_subsequence(dl, pl), f"{f}: not a subsequence of the plain file"
+                gone += len(pl) - len(dl)
+            assert gone == last["consensus_dedup"].get("suppressed"), "suppressed != lines missing"
+        d = os.path.join(work, "timed")
+        _, ph = _run_child("consensus", ROOT, in_dir, d, cfg.box, a.timeout, work,
+                           dedup=a.dedup_ji, dedup_timing=True)
+        shutil.rmtree(d)
+        out["box_files"] = len(plain)
+        for n, _ in arms:
+            out[n + "_s"] = secs[n]
+            out[n + "_median_s"] = statistics.median(secs[n])
+            out[n + "_range_s"] = [min(secs[n]), max(secs[n])]
+            out[n + "_h2d_bytes"] = last[n].get("h2d_bytes")
+            out[n + "_d2h_bytes"] = last[n].get("d2h_bytes")
+            out[n + "_device_s"] = last[n].get("device_s")
+            out[n + "_write_s"] = last[n].get("write_s")
+        dd = last["consensus_dedup"]
+        out["added_median_s"] = out["consensus_dedup_median_s"] - out["consensus_median_s"]
+        out["added_h2d_bytes"] = dd.get("dedup_h2d_bytes")
+        out["added_d2h_bytes"] = dd.get("dedup_d2h_bytes")
+        out["dedup_s"] = dd.get("dedup_s")
+        out["picks_plain"] = last["consensus"].get("picks")
+        out["picks_written"] = dd.get("picks")
+        out["suppressed"] = dd.get("suppressed")
+        out["k_nms_count_ms"] = ph.get("k_nms_count_ms")
+        out["k_nms_ms"] = ph.get("k_nms_ms")
+        out["cliques"] = dd.get("cliques")
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+    path = a.out or os.path.join(ROOT, "profiles", f"consensus_dedup_f2f_{a.config}.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
     print(json.dumps(out))
 
 
