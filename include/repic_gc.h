@@ -446,6 +446,87 @@ typedef struct rgc_pick_members_in {
 int rgc_pick_members(rgc_ctx* ctx, const rgc_pick_members_in* in, rgc_pick_out* out,
                      rgc_members_out* mem);
 
+/* `repic consensus --min_pickers M`: tiered picks agreed by at least M of the k pickers.
+ * Additive symbols: no struct changes layout and RGC_ABI_VERSION stays 11; a caller finds out by
+ * symbol lookup.  Tiers run t = k, k-1, .., M, per micrograph:
+ *   tier k   is rgc_consensus: the same run, packing and picks.
+ *   explain  before tier t < k a box b is explained iff a pick c of a higher tier has
+ *            JI(b, c) > the run's threshold, c the pick's consensus box at its unrounded
+ *            coordinates, JI the reference's f64 quotient (calc_jaccard's operation order, strict
+ *            `>`, the test of rgc_nms); a box with a non-finite coordinate is explained by nothing.
+ *            box_tier[b] = the tier of the first pick that explained b, else 0 (the picks of tier
+ *            M mark their boxes too, so on return box_tier covers every tier).
+ *   tier t   for every subset S of t pickers, in ascending order of the picker-index tuple, the
+ *            unexplained boxes of S's pickers in file order form a pseudo-micrograph (box ids:
+ *            id_base[m] + position).  One with an empty segment is not submitted.  All of a tier's
+ *            pseudo-micrographs go through one run (k' = t, the same threshold), so a tier's
+ *            cliques, weights, confidences and consensus boxes are what rgc_run gives for those
+ *            boxes alone.  One set packing per micrograph over the columns of all its subsets
+ *            (subset order, then the run's clique order; rows are full-batch box indices; weights
+ *            are the run's w), picks in run_ilp's order.  A tier in which nothing can be submitted
+ *            is skipped; the loop ends once no micrograph has M pickers with an unexplained box.
+ * `out` is filled as rgc_consensus fills it: out->run is tier k's run (its per-clique pointers are
+ * NULL once a lower tier made a run, with or without RGC_F_HOST_OUTPUTS: the lower tiers' runs
+ * reuse the context's per-clique arrays), except run.status: RGC_OK iff some tier gave the micrograph a
+ * column, else tier k's.  The pick arrays hold every tier: per micrograph tier descending, then the
+ * tier's own order; pcol is the column within the micrograph's columns of that tier; sel_cnt the
+ * chosen columns summed over tiers; ilp_status the weakest over the tiers that had columns and
+ * ilp_gap the largest.  opts->num_particles keeps the first N picks of that order and is applied
+ * last, on the host: every pick takes part in explaining.
+ * With RGC_F_TIMING the sections "k_vote_explain", "k_vote_gather", the tier's run, "k_vote_cols",
+ * the solver's and "k_pick_emit" follow tier k's, per tier.
+ * Refused before any launch, the context staying usable: null arguments, a submitted run awaiting
+ * rgc_wait, RGC_F_MULTI_OUT or RGC_F_GET_CC, min_pickers outside 2..k. */
+typedef struct rgc_tiers_out {
+  int32_t n_tiers;         /* k - min_pickers + 1; tier index j is tier k - j */
+  /* host memory owned by the context, like the pick arrays */
+  int32_t* ptier;          /* [n_picked] tier of each pick */
+  int32_t* pmask;          /* [n_picked] bit p set: picker p is in the pick's subset */
+  float* pw;               /* [n_picked] the pick's column weight */
+  int32_t* pmember;        /* [n_picked*k] batch box index of picker p's member at i*k+p, else -1 */
+  int32_t* box_tier;       /* [n_boxes] */
+  int64_t* tier_cols;      /* [n_mg*n_tiers] columns of micrograph m in tier index j at m*n_tiers+j */
+  int64_t* tier_picks;     /* [n_mg*n_tiers] picks written (after num_particles) */
+} rgc_tiers_out;
+int rgc_consensus_tiers(rgc_ctx* ctx, const rgc_batch_in* in, const rgc_consensus_opts* opts,
+                        int min_pickers, rgc_consensus_out* out, rgc_tiers_out* tiers);
+
+/* The explain / count / gather kernels alone, on host arrays: test hook, the counterpart of
+ * rgc_pick_select.  The picks of micrograph m, [pick_off[m], pick_off[m+1]) of pcx / pcy, mark the
+ * boxes they explain with pick_tier (box_tier_in, may be NULL: all 0, is the state before); then
+ * the pseudo-batch of tier t is built from the boxes still at 0.  Outputs are owned by the context
+ * (valid until its next call).  Refused before any launch: null arrays, offsets that do not start
+ * at 0 or decrease, k outside 1..8, t outside 1..k, pick_tier < 1, a bad box_size or threshold
+ * and a run awaiting rgc_wait. */
+typedef struct rgc_vote_gather_in {
+  int32_t n_mg;
+  int32_t k;
+  int32_t t;               /* pickers per subset of the pseudo-batch */
+  int32_t pick_tier;       /* what explained boxes are marked with */
+  int64_t box_size;
+  double ji_threshold;
+  const int64_t* box_off;  /* [n_mg*k+1] */
+  const double* x;         /* [n_boxes] */
+  const double* y;
+  const double* score;
+  const int64_t* pick_off; /* [n_mg+1] */
+  const double* pcx;       /* [pick_off[n_mg]] unrounded consensus coordinates */
+  const double* pcy;
+  const int32_t* box_tier_in;  /* [n_boxes] or NULL */
+} rgc_vote_gather_in;
+typedef struct rgc_vote_gather_out {
+  int32_t n_sub;           /* submitted pseudo-micrographs, micrograph-major, subsets ascending */
+  int32_t* sub_mg;         /* [n_sub] */
+  int32_t* sub_mask;       /* [n_sub] picker bitmask of the subset */
+  int64_t* box_off;        /* [n_sub*t+1] the pseudo-batch's offsets */
+  int32_t* box_tier;       /* [n_boxes] after the explain step */
+  int32_t* origin;         /* [box_off[n_sub*t]] batch box index of each pseudo-batch box */
+  double* x;               /* the pseudo-batch */
+  double* y;
+  double* score;
+} rgc_vote_gather_out;
+int rgc_vote_gather(rgc_ctx* ctx, const rgc_vote_gather_in* in, rgc_vote_gather_out* out);
+
 int rgc_parse_files(const char* const* paths, int64_t n_files, int n_threads, rgc_parsed** out);
 void rgc_parsed_free(rgc_parsed* p);
 

@@ -11,16 +11,8 @@
 
 using namespace rgc;
 
-// The per-micrograph host block of the pick stage (H_PK_MG): pick_off, primal, gap (8 B
-// each), then sel_cnt and the ILP status (4 B each).
-struct PickHost {
-  int64_t* pick_off;
-  double* primal;
-  double* gap;
-  int32_t* sel_cnt;
-  int32_t* status;
-};
-static int pick_host(rgc_ctx* c, int n_mg, PickHost* h) {
+// The per-micrograph host block of the pick stage (PickHost, rgc_host.h)
+int pick_host(rgc_ctx* c, int n_mg, PickHost* h) {
   TRY(ensure_host(c, H_PK_MG, ((size_t)n_mg + 1) * 8 + (size_t)n_mg * 24 + 16));
   h->pick_off = H<int64_t>(c, H_PK_MG);
   h->primal = reinterpret_cast<double*>(h->pick_off + n_mg + 1);
@@ -33,7 +25,7 @@ static int pick_host(rgc_ctx* c, int n_mg, PickHost* h) {
 
 // Selection, pick_off scan and emit (rgc_pick.hip) of a batch whose inputs A already names;
 // the picks and the per-micrograph counts land in the context's host buffers.
-static int pick_stage(rgc_ctx* c, rgc::PickArgs& A, const PickHost& h, int64_t* n_picked) {
+int pick_stage(rgc_ctx* c, rgc::PickArgs& A, const PickHost& h, int64_t* n_picked) {
   hipStream_t s = c->stream;
   const int n_mg = A.n_mg;
   *n_picked = 0;
@@ -201,8 +193,27 @@ static int members_stage(rgc_ctx* c, const rgc::PickArgs& A, const PickHost& h, 
   return 0;
 }
 
+void ilp_mg_status(const uint8_t* exact, const double* gap, int64_t j0, int64_t j1, double primal,
+                   int32_t* status, double* rel_gap) {
+  bool all_opt = true, heur = false, nodel = false;
+  double g = 0.0;
+  for (int64_t j = j0; j < j1; ++j) {
+    all_opt = all_opt && exact[j] == RGC_ILP_OPTIMAL;
+    heur = heur || exact[j] == RGC_ILP_HEURISTIC;
+    nodel = nodel || exact[j] == RGC_ILP_NODE_LIMIT;
+    g += gap[j];
+  }
+  int st = RGC_ILP_GAP_OK;
+  if (all_opt) st = RGC_ILP_OPTIMAL;
+  else if (g <= 1e-4 * std::fabs(primal)) st = RGC_ILP_GAP_OK;
+  else if (heur) st = RGC_ILP_HEURISTIC;
+  else if (nodel) st = RGC_ILP_NODE_LIMIT;
+  *status = st;
+  *rel_gap = primal > 0 ? g / primal : (g == 0 ? 0.0 : HUGE_VAL);
+}
+
 // rgc_consensus (mem == nullptr) and rgc_consensus_members
-static int consensus_impl(rgc_ctx* c, const rgc_batch_in* in, const rgc_consensus_opts* opts,
+int consensus_impl(rgc_ctx* c, const rgc_batch_in* in, const rgc_consensus_opts* opts,
                           rgc_consensus_out* out, rgc_members_out* mem) {
   if (!c || !in || !opts || !out) return fail("null argument");
   if (c->pend) return fail("rgc_consensus: a submitted run awaits rgc_wait on this context");
@@ -318,24 +329,9 @@ static int consensus_impl(rgc_ctx* c, const rgc_batch_in* in, const rgc_consensu
   HIPCHK(hipStreamSynchronize(s));
 
   // per-micrograph status and relative gap, reduced as repic_amd.ilp.mg_status does
-  for (int m = 0; m < n_mg; ++m) {
-    bool all_opt = true, heur = false, nodel = false;
-    double g = 0.0;
-    for (int64_t j = col_off[m]; j < col_off[m + 1]; ++j) {
-      all_opt = all_opt && hex[j] == RGC_ILP_OPTIMAL;
-      heur = heur || hex[j] == RGC_ILP_HEURISTIC;
-      nodel = nodel || hex[j] == RGC_ILP_NODE_LIMIT;
-      g += hgap[j];
-    }
-    const double primal = h.primal[m];
-    int st = RGC_ILP_GAP_OK;
-    if (all_opt) st = RGC_ILP_OPTIMAL;
-    else if (g <= 1e-4 * std::fabs(primal)) st = RGC_ILP_GAP_OK;
-    else if (heur) st = RGC_ILP_HEURISTIC;
-    else if (nodel) st = RGC_ILP_NODE_LIMIT;
-    h.status[m] = st;
-    h.gap[m] = primal > 0 ? g / primal : (g == 0 ? 0.0 : HUGE_VAL);
-  }
+  for (int m = 0; m < n_mg; ++m)
+    ilp_mg_status(hex.data(), hgap.data(), col_off[m], col_off[m + 1], h.primal[m], &h.status[m],
+                  &h.gap[m]);
 
   // what crossed the bus in this call (the solver's per-column x / status / gap included)
   const int64_t N = R.n_boxes;

@@ -357,6 +357,16 @@ __device__ __forceinline__ int64_t block_scan_u16(uint16_t* a, int n, int64_t* l
   return tot;
 }
 
+// the last m with off[m] <= i (off[0] <= i < off[n]; empty ranges skipped)
+__device__ __forceinline__ int range_of(const int64_t* off, int n, int64_t i) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= i) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // ----------------------------------------------------------------------------- arithmetic
 // overlap area of two boxes, reference op order (get_cliques.py:42-44), no FMA.
 __host__ __device__ __forceinline__ double overlap(double x, double y, double a, double b, double B) {

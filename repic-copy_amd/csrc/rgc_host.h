@@ -74,6 +74,13 @@ enum DevBufId {
   // per-segment edges and results
   D_NM_OFF, D_NM_NS, D_NM_XY, D_NM_SXY, D_NM_SIDX, D_NM_STATE, D_NM_ETOT, D_NM_EBASE, D_NM_ADJ,
   D_NM_KEEP, D_NM_KEPT, D_NM_STAT,
+  // consensus --min_pickers (rgc_vote.hip): the full batch's offsets and box tiers, per-segment
+  // counts, the pseudo-batch (segment sources and found counts, offsets, x / y / score, origin),
+  // its pseudo-micrograph table, the tier's packed per-column arrays, per-micrograph column
+  // offsets, the tier's per-pick arrays, the bad-index flag, and the hook's uploaded boxes / picks
+  D_VT_BOXOFF, D_VT_TIER, D_VT_SEGCNT, D_VT_PSEG, D_VT_PBOXOFF, D_VT_GX, D_VT_GY, D_VT_GS,
+  D_VT_ORIGIN, D_VT_QMETA, D_VT_CW, D_VT_CCONF, D_VT_CCONS, D_VT_CMEMB, D_VT_CMASK, D_VT_COLOFF,
+  D_VT_PCX, D_VT_PCY, D_VT_PW, D_VT_PMASK, D_VT_PMEMB, D_VT_BAD, D_VT_HXYS, D_VT_HPOFF,
   D_COUNT
 };
 enum HostBufId {
@@ -84,7 +91,11 @@ enum HostBufId {
   H_PK_META, H_PK_MG, H_PK_PX, H_PK_PY, H_PK_PCONF, H_PK_PCOL,
   // consensus --members: segment metadata staging (then left_off), member and leftover
   // coordinates, per-segment counts
-  H_PM_META, H_PM_X, H_PM_Y, H_PM_LX, H_PM_LY, H_PM_SEG, H_COUNT
+  H_PM_META, H_PM_X, H_PM_Y, H_PM_LX, H_PM_LY, H_PM_SEG,
+  // consensus --min_pickers: the per-micrograph block (tier k's run stats, pick_off, the ILP
+  // summary, per-tier counts), the pick block, box_tier, staging of counts and per-pick arrays,
+  // and the gather hook's outputs
+  H_VT_MG, H_VT_PICK, H_VT_BOXTIER, H_VT_STAGE, H_VT_SUB, H_VT_ORIGIN, H_VT_GXYS, H_COUNT
 };
 
 struct Buf {
@@ -180,3 +191,25 @@ int run_multi(rgc_ctx* c, int n_mg, int k, double B, double two_b2, const rgc::J
 // the CSC arrays are already in D_IL_CPTR / D_IL_ROW / D_IL_W with dev_k rows per column.
 int ilp_solve_rec(rgc_ctx* c, const rgc_ilp_in* in, uint8_t* x, uint8_t* exact, double* gap,
                   int depth, int dev_k = 0);
+
+// ---- rgc_consensus and its pick stage (rgc_consensus.cpp), shared with rgc_vote_host.cpp
+// rgc_consensus (mem == nullptr) and rgc_consensus_members
+int consensus_impl(rgc_ctx* c, const rgc_batch_in* in, const rgc_consensus_opts* opts,
+                   rgc_consensus_out* out, rgc_members_out* mem);
+// The per-micrograph host block of the pick stage (H_PK_MG): pick_off, primal, gap (8 B
+// each), then sel_cnt and the ILP status (4 B each).
+struct PickHost {
+  int64_t* pick_off;
+  double* primal;
+  double* gap;
+  int32_t* sel_cnt;
+  int32_t* status;
+};
+int pick_host(rgc_ctx* c, int n_mg, PickHost* h);
+// Selection, pick_off scan and emit (rgc_pick.hip) of a batch whose inputs A already names;
+// the picks and the per-micrograph counts land in the context's host buffers.
+int pick_stage(rgc_ctx* c, rgc::PickArgs& A, const PickHost& h, int64_t* n_picked);
+// A micrograph's ILP status and relative gap from its columns' [j0, j1) component statuses and
+// gaps and its packing value, reduced as repic_amd.ilp.mg_status does.
+void ilp_mg_status(const uint8_t* exact, const double* gap, int64_t j0, int64_t j1, double primal,
+                   int32_t* status, double* rel_gap);

@@ -553,4 +553,91 @@ struct PickMemArgs {
 void launch_pick_members(hipStream_t stream, const PickMemArgs& A);   // marks + member emit
 void launch_pick_left(hipStream_t stream, const PickMemArgs& A);      // leftover compaction
 
+// consensus --min_pickers (rgc_vote.hip): which boxes the picks of the tiers so far explain, and
+// the pseudo-batch of a lower tier built from the boxes they leave.  Segment s = m * k + p holds
+// the boxes [box_off[s], box_off[s + 1]) of picker p of micrograph m, as in PickMemArgs.
+constexpr int VOTE_TILE = 256;   // picks per LDS tile of k_vote_explain
+struct VoteArgs {
+  int n_mg, k;
+  double B, two_b2, thr;      // explained <=> jaccard(box, pick, B, two_b2) > thr
+  const int64_t* box_off;     // [n_mg * k + 1]
+  const double* bx;
+  const double* by;
+  const double* bs;           // scores (k_vote_gather)
+  int32_t* box_tier;          // [n_boxes] tier of the first pick that explained the box, else 0
+  // k_vote_explain: the picks of micrograph m, [pick_off[m], pick_off[m + 1]), unrounded
+  int tier;
+  const int64_t* pick_off;    // [n_mg + 1]
+  const double* pcx;
+  const double* pcy;
+  // k_vote_count
+  int32_t* seg_cnt;           // [n_mg * k] boxes of the segment with box_tier == 0
+  // k_vote_gather: pseudo-batch segment u takes the unexplained boxes of segment pseg_src[u], in
+  // file order, at [pbox_off[u], pbox_off[u + 1]); nothing is written past that range
+  int n_pseg;
+  const int32_t* pseg_src;    // [n_pseg]
+  const int64_t* pbox_off;    // [n_pseg + 1]
+  double* gx;
+  double* gy;
+  double* gs;
+  int32_t* origin;            // [pbox_off[n_pseg]] full-batch index of each pseudo-batch box
+  int32_t* pseg_cnt;          // [n_pseg] unexplained boxes found (the host compares it with the range)
+};
+void launch_vote_explain(hipStream_t stream, const VoteArgs& A);
+void launch_vote_count(hipStream_t stream, const VoteArgs& A);
+void launch_vote_gather(hipStream_t stream, const VoteArgs& A);
+
+// k_vote_cols, k_pick_cols' sibling for a tier of t-cliques: pseudo-micrograph q (of micrograph
+// q_mg[q], picker subset q_mask[q]) owns columns [qcol_off[q], qcol_off[q + 1]), whose per-clique
+// data start at q_src[q] in the tier's run.  Pseudo-micrographs are ordered micrograph-major, so a
+// micrograph's columns are contiguous.  Besides the solver's CSC inputs the kernel packs, in
+// column order, what the pick stage and k_vote_picks read (full-batch box indices throughout).
+struct VoteColArgs {
+  int n_q, t;
+  int64_t n_cols, n_pbox, n_box;
+  const int64_t* qcol_off;    // [n_q + 1]
+  const int64_t* q_src;       // [n_q]
+  const int32_t* q_mg;        // [n_q]
+  const int32_t* q_mask;      // [n_q]
+  const int32_t* origin;      // [n_pbox]
+  const int32_t* members;     // [C * t] pseudo-batch box indices, picker order (the run's)
+  const float* w;
+  const float* conf;
+  const int32_t* cons;        // [C] pseudo-batch box index
+  int64_t* col_ptr;           // [n_cols + 1]
+  int32_t* row_idx;           // [n_cols * t]
+  double* w64;
+  int32_t* col_mg;
+  float* cw;                  // [n_cols]
+  float* cconf;
+  int32_t* ccons;
+  int32_t* cmemb;             // [n_cols * t]
+  int32_t* cmask;             // [n_cols]
+  int32_t* bad;               // [1] zeroed: set when a member or consensus index is out of range
+};
+void launch_vote_cols(hipStream_t stream, const VoteColArgs& A);
+
+// k_vote_picks: per written pick of the tier (k_pick_emit's pick_off / pcol) its unrounded
+// consensus coordinates, column weight, picker mask and members by picker (-1 outside the mask).
+struct VotePickArgs {
+  int n_mg, k, t;
+  int64_t n_picked, n_box;
+  const int64_t* pick_off;    // [n_mg + 1]
+  const int32_t* pcol;
+  const int64_t* col_off;     // [n_mg + 1]
+  const int64_t* src_base;    // [n_mg] or nullptr: the column arrays are packed (col_off[m] + pcol)
+  const int32_t* cons;        // full-batch box of the consensus coordinates
+  const int32_t* members;     // [.. * t] full-batch box indices, picker order
+  const int32_t* cmask;       // picker mask of each column, or nullptr: all k pickers
+  const float* w;
+  const double* bx;
+  const double* by;
+  double* pcx;
+  double* pcy;
+  float* pw;
+  int32_t* pmask;
+  int32_t* pmember;           // [n_picked * k]
+};
+void launch_vote_picks(hipStream_t stream, const VotePickArgs& A);
+
 }  // namespace rgc

@@ -18,6 +18,7 @@
 // gfx950, wave64.  One 256-thread workgroup per micrograph in the per-micrograph kernels.
 #include <hip/hip_runtime.h>
 
+#include "rgc_device.h"
 #include "rgc_kernels.h"
 
 namespace rgc {
@@ -32,13 +33,7 @@ __global__ __launch_bounds__(PK_NT) void k_pick_cols(PickArgs A) {
   const int64_t c = (int64_t)blockIdx.x * PK_NT + threadIdx.x;
   if (c == 0) A.col_ptr[A.n_cols] = A.n_cols * A.k;
   if (c >= A.n_cols) return;
-  // micrograph of column c: the last m with col_off[m] <= c (empty micrographs skipped)
-  int lo = 0, hi = A.n_mg;   // col_off[lo] <= c < col_off[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (A.col_off[mid] <= c) lo = mid; else hi = mid;
-  }
-  const int m = lo;
+  const int m = range_of(A.col_off, A.n_mg, c);   // (empty micrographs skipped)
   const int64_t src = A.src_base[m] + (c - A.col_off[m]);
   const int32_t rb = (int32_t)A.row_base[m];
   for (int j = 0; j < A.k; ++j) A.row_idx[c * A.k + j] = A.rows[src * A.k + j] + rb;
@@ -154,16 +149,6 @@ __global__ __launch_bounds__(PK_NT) void k_pick_emit(PickArgs A) {
 }
 
 // ---- consensus --members: launched only when members are asked for (PickMemArgs)
-
-// the last m with off[m] <= i (off[0] <= i < off[n]; empty ranges skipped)
-__device__ inline int range_of(const int64_t* off, int n, int64_t i) {
-  int lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 // One thread per column: its k member boxes are "in some clique".  Every writer stores the
 // same byte value, so concurrent stores to one address need no atomic; the marks of written

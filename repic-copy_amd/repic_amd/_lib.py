@@ -161,6 +161,42 @@ if has_nms():
     lib.rgc_nms.argtypes = [C.c_void_p, C.POINTER(NmsIn), C.c_void_p, C.c_void_p]
     lib.rgc_nms_last_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
 
+class TiersOut(C.Structure):
+    _fields_ = [("n_tiers", C.c_int32), ("ptier", _i32p), ("pmask", _i32p), ("pw", _f32p),
+                ("pmember", _i32p), ("box_tier", _i32p), ("tier_cols", _i64p),
+                ("tier_picks", _i64p)]
+
+
+class VoteGatherIn(C.Structure):
+    _fields_ = [("n_mg", C.c_int32), ("k", C.c_int32), ("t", C.c_int32),
+                ("pick_tier", C.c_int32), ("box_size", C.c_int64), ("ji_threshold", C.c_double),
+                ("box_off", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p),
+                ("score", C.c_void_p), ("pick_off", C.c_void_p), ("pcx", C.c_void_p),
+                ("pcy", C.c_void_p), ("box_tier_in", C.c_void_p)]
+
+
+class VoteGatherOut(C.Structure):
+    _fields_ = [("n_sub", C.c_int32), ("sub_mg", _i32p), ("sub_mask", _i32p),
+                ("box_off", _i64p), ("box_tier", _i32p), ("origin", _i32p), ("x", _f64p),
+                ("y", _f64p), ("score", _f64p)]
+
+
+TIERS_SYMBOLS = ("rgc_consensus_tiers", "rgc_vote_gather")
+TIERS_SUFFIX = "_tiers.tsv"
+
+
+def has_tiers() -> bool:
+    """The loaded library has the ``consensus --min_pickers`` entry points (additive symbols:
+    the ABI version does not tell)."""
+    return all(hasattr(lib, n) for n in TIERS_SYMBOLS)
+
+
+if has_tiers():
+    lib.rgc_consensus_tiers.argtypes = [C.c_void_p, C.POINTER(BatchIn), C.POINTER(ConsensusOpts),
+                                        C.c_int, C.POINTER(ConsensusOut), C.POINTER(TiersOut)]
+    lib.rgc_vote_gather.argtypes = [C.c_void_p, C.POINTER(VoteGatherIn),
+                                    C.POINTER(VoteGatherOut)]
+
 lib.rgc_abi_version.restype = C.c_int
 lib.rgc_consensus.argtypes = [C.c_void_p, C.POINTER(BatchIn), C.POINTER(ConsensusOpts),
                               C.POINTER(ConsensusOut)]
@@ -207,7 +243,8 @@ EXPORTS = ["rgc_abi_version", "rgc_last_error", "rgc_device_count", "rgc_ctx_cre
            "rgc_parsed_free", "rgc_py_hash_node", "rgc_py_set_order", "rgc_test_epilogue",
            "rgc_score_pairs", "rgc_score_sweep", "rgc_score_match", "rgc_score_match_sweep", "rgc_test_iou_edge", "rgc_ilp_solve", "rgc_write_outputs", "rgc_pickle_bytes",
            "rgc_py_float_repr", "rgc_consensus", "rgc_pick_select", "rgc_write_boxes",
-           "rgc_np_float_str", "rgc_test_ji_cutoff", *MEMBERS_SYMBOLS, *NMS_SYMBOLS]
+           "rgc_np_float_str", "rgc_test_ji_cutoff", *MEMBERS_SYMBOLS, *NMS_SYMBOLS,
+           *TIERS_SYMBOLS]
 
 
 class RGCError(RuntimeError):
@@ -502,6 +539,75 @@ class Context:
         del keep
         return ConsensusResult(co, self._result(co.run, n_mg, k, flags), n_mg, mo, k)
 
+    def consensus_tiers(self, n_mg, k, box_size, box_off, id_base, x, y, score, min_pickers,
+                        flags=0, dev_meta=None, node_limit=0, num_particles=None, timing=False,
+                        ji_threshold=None):
+        """``consensus`` with tiers k, k-1, .., ``min_pickers`` (rgc_consensus_tiers): each lower
+        tier packs the cliques of every subset of t pickers among the boxes the picks of the
+        tiers above leave unexplained.  The :class:`ConsensusResult` holds every tier's picks
+        (per micrograph tier descending, then the tier's order) and also ``ptier``, ``pmask``
+        (picker bitmask), ``pw``, ``pmember`` [n_picked, k] (batch box index or -1),
+        ``box_tier`` [n_boxes], ``tier_cols`` and ``tier_picks`` [n_mg, k - min_pickers + 1]
+        (column j: tier k - j)."""
+        _need_tiers()
+        bi, keep, flags = self._batch_in(n_mg, k, box_size, box_off, id_base, x, y, score, flags,
+                                         dev_meta, ji_threshold)
+        self._retire()
+        opts = ConsensusOpts(int(node_limit), -1 if num_particles is None else int(num_particles),
+                             F_TIMING if timing else 0)
+        co, to = ConsensusOut(), TiersOut()
+        _check(lib.rgc_consensus_tiers(self._p, C.byref(bi), C.byref(opts), int(min_pickers),
+                                       C.byref(co), C.byref(to)))
+        n_boxes = int(keep[0][-1]) if len(keep[0]) else 0
+        del keep
+        # (the run's per-clique arrays are not handed out: the lower tiers reuse them)
+        r = ConsensusResult(co, self._result(co.run, n_mg, k, flags & ~F_HOST_OUTPUTS), n_mg)
+        n, nt = r.n_picked, int(to.n_tiers)
+        r.ptier = _copy(to.ptier, n, np.int32)
+        r.pmask = _copy(to.pmask, n, np.int32)
+        r.pw = _copy(to.pw, n, np.float32)
+        r.pmember = _copy(to.pmember, n * k, np.int32).reshape(n, k)
+        r.box_tier = _copy(to.box_tier, n_boxes, np.int32)
+        r.tier_cols = _copy(to.tier_cols, n_mg * nt, np.int64).reshape(n_mg, nt)
+        r.tier_picks = _copy(to.tier_picks, n_mg * nt, np.int64).reshape(n_mg, nt)
+        return r
+
+    def vote_gather(self, k, t, box_size, ji_threshold, box_off, x, y, score, pick_off, pcx, pcy,
+                    pick_tier=None, box_tier=None):
+        """Test hook of the explain / count / gather kernels (rgc_vote_gather): the picks of
+        micrograph m (``pick_off[m]:pick_off[m+1]`` of ``pcx`` / ``pcy``, unrounded) mark the
+        boxes they explain with ``pick_tier`` (default t + 1), starting from ``box_tier`` (None:
+        all 0); the boxes still at 0 then form the pseudo-batch of tier ``t`` -> (box_tier,
+        sub_mg, sub_mask, box_off', origin, x', y', score') copies."""
+        _need_tiers()
+        box_off = np.ascontiguousarray(box_off, np.int64)
+        pick_off = np.ascontiguousarray(pick_off, np.int64)
+        x, y, score, pcx, pcy = (np.ascontiguousarray(v, np.float64)
+                                 for v in (x, y, score, pcx, pcy))
+        n_mg = len(pick_off) - 1
+        n = int(box_off[-1])
+        assert n_mg >= 0 and len(box_off) == n_mg * k + 1
+        assert x.shape == y.shape == score.shape == (n,)
+        assert pcx.shape == pcy.shape == (int(pick_off[-1]),)
+        bt = None
+        if box_tier is not None:
+            bt = np.ascontiguousarray(box_tier, np.int32)
+            assert bt.shape == (n,)
+        gi = VoteGatherIn(n_mg, int(k), int(t), int(t + 1 if pick_tier is None else pick_tier),
+                          int(box_size), float(ji_threshold), box_off.ctypes.data, x.ctypes.data,
+                          y.ctypes.data, score.ctypes.data, pick_off.ctypes.data,
+                          pcx.ctypes.data, pcy.ctypes.data, None if bt is None else bt.ctypes.data)
+        go = VoteGatherOut()
+        self._retire()
+        _check(lib.rgc_vote_gather(self._p, C.byref(gi), C.byref(go)))
+        nq = int(go.n_sub)
+        boff = _copy(go.box_off, nq * t + 1, np.int64)
+        npb = int(boff[-1])
+        return (_copy(go.box_tier, n, np.int32), _copy(go.sub_mg, nq, np.int32),
+                _copy(go.sub_mask, nq, np.int32), boff, _copy(go.origin, npb, np.int32),
+                _copy(go.x, npb, np.float64), _copy(go.y, npb, np.float64),
+                _copy(go.score, npb, np.float64))
+
     def pick_members(self, k, col_off, x, conf, cons, members, box_off, bx, by,
                      num_particles=None):
         """Test hook of the members kernels (rgc_pick_members): ``pick_select`` on columns whose
@@ -637,6 +743,9 @@ class ConsensusResult:
         # with members=True: members of pick i (pmx[i, p]), leftovers of segment s = m k + p
         # (left_off[s]:left_off[s+1] of left_x / left_y) and its boxes in some clique
         self.pmx = self.pmy = self.left_off = self.left_x = self.left_y = self.in_clique = None
+        # consensus_tiers fills these
+        self.ptier = self.pmask = self.pw = self.pmember = self.box_tier = None
+        self.tier_cols = self.tier_picks = None
         if mo is not None:
             S = n_mg * k
             self.pmx = _copy(mo.pmx, self.n_picked * k, np.float64).reshape(self.n_picked, k)
@@ -698,6 +807,12 @@ def _need_members():
     if not has_members():
         raise RGCError(f"{LIB_PATH} has no consensus --members entry points "
                        f"({', '.join(MEMBERS_SYMBOLS)}): rebuild it")
+
+
+def _need_tiers():
+    if not has_tiers():
+        raise RGCError(f"{LIB_PATH} has no consensus --min_pickers entry points "
+                       f"({', '.join(TIERS_SYMBOLS)}): rebuild it")
 
 
 def _need_nms():

@@ -38,6 +38,15 @@ first N survivors are written.  ``consensus_dedup.tsv`` (one row per ok microgra
 was picked, suppressed and written.  ``--dedup_ji`` with ``--members`` is refused (the members of
 a suppressed pick would have to become leftovers, which is not defined yet).
 
+``--min_pickers M`` (2 <= M <= k) adds the particles on which at least M of the k pickers agree,
+in tiers: full agreement first (exactly the plain output, which every ``.box`` starts with), then
+for t = k-1 .. M the cliques of every subset of t pickers among the boxes that no pick so far
+explains (a box is explained when its JI with a pick's consensus box exceeds the run's
+threshold), one set packing per micrograph and tier (``rgc_consensus_tiers``).  Next to each
+``<base>.box`` a ``<base>_tiers.tsv`` names, line by line, the tier and the pickers of each
+written pick, and ``consensus_tiers.tsv`` counts the columns and picks per tier.  A micrograph is
+ok when some tier has a clique.  ``--min_pickers`` with ``--get_cc`` or ``--members`` is refused.
+
 There is no multi-rank form yet: with ``WORLD_SIZE > 1`` the command raises
 before it creates a device context or touches ``out_dir``.
 """
@@ -66,6 +75,10 @@ PICKERS_HEADER = "base\tpicker\tboxes\tin_clique\tin_consensus\n"
 # --dedup_ji: one line per ok micrograph
 DEDUP = "consensus_dedup.tsv"
 DEDUP_HEADER = "base\tpicked\tsuppressed\twritten\n"
+# --min_pickers: one line per ok micrograph (columns and picks per tier k..M), and next to every
+# <base>.box the tier and pickers of each of its lines
+TIERS = "consensus_tiers.tsv"
+TIERS_SUFFIX = _lib.TIERS_SUFFIX
 
 # phase seconds, counts and the library's host<->device byte counts of the last run in this
 # process (tools/consensus_bench.py reads them)
@@ -86,6 +99,10 @@ def add_arguments(parser):
     parser.add_argument("--members", action="store_true",
                         help="also write <base>_members.tsv (per pick its box from every picker, "
                              "then every picker's boxes in no pick) and consensus_pickers.tsv")
+    parser.add_argument("--min_pickers", type=int, default=None, metavar="M",
+                        help="also pick particles on which at least M of the k pickers agree "
+                             "(int, 2 <= M <= k; default: all k), in tiers below the full "
+                             "agreement; also writes <base>_tiers.tsv and consensus_tiers.tsv")
     gc.add_ji_threshold(parser)
     parser.add_argument("--dedup_ji", type=gc._ji_type, default=None, metavar="T",
                         help="drop a written pick whose Jaccard index with a pick written before "
@@ -112,6 +129,7 @@ def main(args):
             "repic consensus: --dedup_ji and --members cannot be combined: the members of a "
             "suppressed pick would have to become leftovers, which is not defined yet "
             "(nothing was deleted or written)")
+    min_pickers_of(args)       # (likewise)
     world, rank, local = gc._dist_env()
     if world > 1:
         raise _lib.RGCError(
@@ -147,6 +165,10 @@ def main(args):
                 with open(os.path.join(args.out_dir, DEDUP), "wt") as o:
                     o.write(DEDUP_HEADER)
                     o.writelines(runs[0].dedup_rows)
+            if runs[0].min_pickers is not None:
+                with open(os.path.join(args.out_dir, TIERS), "wt") as o:
+                    o.write(tiers_header(runs[0].k, runs[0].min_pickers))
+                    o.writelines(runs[0].tier_rows)
 
 
 def dedup_ji_of(args):
@@ -154,6 +176,29 @@ def dedup_ji_of(args):
     the option (also when a hand-built namespace lacks it)."""
     t = getattr(args, "dedup_ji", None)
     return None if t is None else _lib.check_ji_threshold(t)
+
+
+def min_pickers_of(args):
+    """The run's ``--min_pickers`` M, validated before a context exists or anything is deleted
+    (RGCError: with --get_cc or --members, or outside 2..k), or None without the option."""
+    m = getattr(args, "min_pickers", None)
+    if m is None:
+        return None
+    for flag in ("get_cc", "members"):
+        if getattr(args, flag, False):
+            raise _lib.RGCError(
+                f"repic consensus: --min_pickers and --{flag} cannot be combined "
+                "(nothing was deleted or written)")
+    k = len(gc._methods_after_reset(args.in_dir, args.out_dir))
+    if not 2 <= int(m) <= k:
+        raise _lib.RGCError(
+            f"repic consensus: --min_pickers must be in 2..{k} (the picker directories of "
+            f"{args.in_dir}), got {m} (nothing was deleted or written)")
+    return int(m)
+
+
+def tiers_header(k, m):
+    return "base" + "".join(f"\tcols_{t}\tpicks_{t}" for t in range(k, m - 1, -1)) + "\n"
 
 
 class _Res:
@@ -165,6 +210,9 @@ class _Res:
     # --members: per pick (rows of k), per segment (micrograph, picker), per leftover
     MEMBERS = ("pmx", "pmy", "seg_boxes", "in_clique", "left_x", "left_y")
 
+    # --min_pickers: per pick, and per micrograph the columns of each tier
+    TIERS = ("ptier", "pmask", "tier_cols")
+
     def __init__(self, r, box_off=None, dedup=None):
         # --dedup_ji: (picks the device returned, picks suppressed) per micrograph
         self.dedup = dedup is not None
@@ -175,6 +223,9 @@ class _Res:
         self.sel_cnt, self.ilp_status, self.ilp_gap = r.sel_cnt, r.ilp_status, r.ilp_gap
         self.pick_off = r.pick_off
         self.px, self.py, self.pconf = r.px, r.py, r.pconf
+        self.tiers = r.ptier is not None
+        if self.tiers:
+            self.ptier, self.pmask, self.tier_cols = r.ptier, r.pmask, r.tier_cols
         self.members = r.pmx is not None
         if self.members:
             self.pmx, self.pmy, self.in_clique = r.pmx, r.pmy, r.in_clique
@@ -191,6 +242,9 @@ class _Res:
         if self.dedup:
             self.picked = np.concatenate([self.picked, o.picked])
             self.suppressed = np.concatenate([self.suppressed, o.suppressed])
+        if self.tiers:
+            for f in self.TIERS:
+                setattr(self, f, np.concatenate([getattr(self, f), getattr(o, f)]))
         if self.members:
             for f in self.MEMBERS:
                 setattr(self, f, np.concatenate([getattr(self, f), getattr(o, f)]))
@@ -213,6 +267,10 @@ class _Run(gc._Run):
         self.dedup_rows = []
         if self.dedup is not None:
             self.stats.update(suppressed=0, dedup_s=0.0, dedup_h2d_bytes=0, dedup_d2h_bytes=0)
+        self.min_pickers = getattr(self.args, "min_pickers", None)
+        self.tier_rows = []
+        if self.min_pickers is not None:
+            self.stats.update({f"picks_tier_{t}": 0 for t in range(self.min_pickers, self.k + 1)})
 
     def device(self, ch):
         ch.res = None
@@ -228,13 +286,26 @@ class _Run(gc._Run):
         for m0, m1 in split_batches(np.diff(b.box_off[::self.k]).tolist(),
                                     getattr(self.args, "batch_boxes", 1 << 25)):
             part = b if (m0 == 0 and m1 == b.n_mg) else b.slice(m0, m1)
-            r = self.ctx.consensus(part.n_mg, part.k, part.box_size, part.box_off, part.id_base,
-                                   part.x, part.y, part.score, flags,
-                                   node_limit=getattr(self.args, "node_limit", 0) or 0,
-                                   num_particles=(self.args.num_particles
-                                                  if self.dedup is None else None),
-                                   ji_threshold=self.ji, **({"members": True} if self.members
-                                                            else {}))
+            more = {"members": True} if self.members else {}
+            call = self.ctx.consensus
+            if self.min_pickers is not None and self.min_pickers < self.k:
+                call, more = self.ctx.consensus_tiers, {"min_pickers": self.min_pickers}
+                if getattr(self.args, "tiers_timing", False):
+                    more["timing"] = True
+            r = call(part.n_mg, part.k, part.box_size, part.box_off, part.id_base,
+                     part.x, part.y, part.score, flags=flags,
+                     node_limit=getattr(self.args, "node_limit", 0) or 0,
+                     num_particles=(self.args.num_particles if self.dedup is None else None),
+                     ji_threshold=self.ji, **more)
+            if more.get("timing"):
+                for nm, ms in self.ctx.kernel_times():
+                    self.stats[nm + "_ms"] = self.stats.get(nm + "_ms", 0.0) + ms
+            if self.min_pickers is not None and r.ptier is None:
+                # --min_pickers k: the plain call; every pick is of tier k, by all pickers
+                r.ptier = np.full(r.n_picked, self.k, np.int32)
+                r.pmask = np.full(r.n_picked, (1 << self.k) - 1, np.int32)
+                okc = np.asarray(r.run.status) == _lib.OK
+                r.tier_cols = np.where(okc, np.asarray(r.run.clique_cnt), 0)[:, None].astype(np.int64)
             self.stats["h2d_bytes"] += r.h2d_bytes
             self.stats["d2h_bytes"] += r.d2h_bytes
             if self.dedup is not None:
@@ -245,7 +316,8 @@ class _Run(gc._Run):
         self.stats["device_s"] += time.time() - t0
         ok = ch.res.status == _lib.OK
         self.stats["edges"] += int(ch.res.n_edges_mg[ok].sum())
-        self.stats["cliques"] += int(ch.res.clique_cnt[ok].sum())
+        self.stats["cliques"] += int(ch.res.tier_cols[ok].sum() if ch.res.tiers
+                                     else ch.res.clique_cnt[ok].sum())
 
     def _suppress(self, r, box_size):
         """--dedup_ji on one consensus call's picks, in place: every micrograph's lines are one
@@ -274,6 +346,8 @@ class _Run(gc._Run):
         off = np.concatenate([[0], np.cumsum(written)])[r.pick_off].astype(np.int64)
         r.pick_off = off
         r.px, r.py, r.pconf, r.pcol = r.px[written], r.py[written], r.pconf[written], r.pcol[written]
+        if r.ptier is not None:
+            r.ptier, r.pmask = r.ptier[written], r.pmask[written]
         r.n_picked = int(off[-1])
         self.stats["suppressed"] += int(picked.sum() - kept.sum())
         self.stats["dedup_s"] += time.time() - t0
@@ -335,8 +409,11 @@ class _Run(gc._Run):
                 if r.dedup:
                     self.dedup_rows.append(
                         f"{mg.base}\t{int(r.picked[s])}\t{int(r.suppressed[s])}\t{n}\n")
+                n_cl = int(r.clique_cnt[s])
+                if r.tiers:
+                    n_cl = self._write_tiers(mg.base, r, s)
                 self.summary.append(
-                    f"{mg.base}\tok\t{int(r.clique_cnt[s])}\t{n}\t{int(r.cc_max[s])}\t"
+                    f"{mg.base}\tok\t{n_cl}\t{n}\t{int(r.cc_max[s])}\t"
                     f"{int(r.cc_cnt[s])}\t{STATUS_NAMES[st]}\t{float(r.ilp_gap[s]):.3e}\n")
                 self.stats["micrographs"] += 1
                 self.stats["picks"] += n
@@ -345,6 +422,28 @@ class _Run(gc._Run):
         flush()
         self.stats["write_s"] += time.time() - t0
         return raise_at
+
+    def _write_tiers(self, base, r, s):
+        """--min_pickers: ``<base>_tiers.tsv`` (line i: the tier and the comma-joined pickers of
+        ``.box`` line i, from the arrays the ``.box`` is written from) and the micrograph's row of
+        consensus_tiers.tsv -> its columns summed over the tiers."""
+        k, p0, p1 = self.k, int(r.pick_off[s]), int(r.pick_off[s + 1])
+        tier, mask = r.ptier[p0:p1], r.pmask[p0:p1]
+        # one string per distinct (tier, subset), then one join: no per-line formatting
+        codes, inv = np.unique(tier.astype(np.int64) << 8 | mask, return_inverse=True)
+        kinds = np.array([f"{c >> 8}\t" + ",".join(self.methods[p] for p in range(k)
+                                                   if (c >> p) & 1) + "\n"
+                          for c in codes.tolist()], dtype=object)
+        with open(os.path.join(self.args.out_dir, base + TIERS_SUFFIX), "wt") as o:
+            o.write("".join(kinds[inv].tolist()))
+        cols = r.tier_cols[s]
+        row = [base]
+        for j, t in enumerate(range(k, self.min_pickers - 1, -1)):
+            picks = int((tier == t).sum())
+            row += [str(int(cols[j]) if j < len(cols) else 0), str(picks)]
+            self.stats[f"picks_tier_{t}"] += picks
+        self.tier_rows.append("\t".join(row) + "\n")
+        return int(cols.sum())
 
     def raise_for(self, mg, ch):
         if mg is self._empty:

@@ -22,6 +22,13 @@ be a subsequence of (a)'s lines and the lines missing must add up to the run's `
 One more run of (b), outside the medians, records the device milliseconds of ``k_nms_count`` and
 ``k_nms`` (RGC_F_TIMING).  The result also goes to ``--out`` (default
 ``profiles/consensus_dedup_f2f_<config>.json``).
+``--min_pickers M`` measures ``consensus --min_pickers M`` instead: per repeat, interleaved, (a)
+plain consensus with the library ``--baseline-lib`` names (the parent commit's build; without it
+this checkout's), (b) plain consensus and (c) ``consensus --min_pickers M`` from this checkout.
+The ``.box`` files of (a) and (b) must be byte-identical and every ``.box`` of (c) must start with
+(b)'s bytes.  One more run of (c), outside the medians, records the per-kernel device
+milliseconds (RGC_F_TIMING).  The result also goes to ``--out`` (default
+``profiles/consensus_tiers_f2f_<config>.json``).
 Prints one JSON line.
 """
 from __future__ import annotations
@@ -58,6 +65,9 @@ def _child(a):
         if a.with_dedup is not None:
             ns.dedup_ji = a.with_dedup
             ns.dedup_timing = a.dedup_timing
+        if a.with_min_pickers is not None:
+            ns.min_pickers = a.with_min_pickers
+            ns.tiers_timing = a.tiers_timing
     with open(os.devnull, "w") as null:
         so, sys.stdout = sys.stdout, null     # the per-micrograph banner lines
         try:
@@ -73,7 +83,7 @@ def _child(a):
 
 
 def _run_child(cmd, root, in_dir, out_dir, box, limit, work, members=False, dedup=None,
-               dedup_timing=False):
+               dedup_timing=False, min_pickers=None, tiers_timing=False, lib=None):
     """-> (wall seconds, the child's phase dict); raises on a non-zero exit."""
     result = os.path.join(work, f"res_{cmd}.json")
     if os.path.exists(result):
@@ -83,8 +93,11 @@ def _run_child(cmd, root, in_dir, out_dir, box, limit, work, members=False, dedu
             "--box", str(box), "--result", result] + (["--with_members"] if members else [])
     if dedup is not None:
         argv += ["--with_dedup", repr(float(dedup))] + (["--dedup_timing"] if dedup_timing else [])
+    if min_pickers is not None:
+        argv += ["--with_min_pickers", str(min_pickers)] + (["--tiers_timing"] if tiers_timing else [])
+    env = dict(os.environ, REPIC_GC_LIB=os.path.abspath(lib)) if lib else None
     t0 = time.perf_counter()
-    r = subprocess.run(argv, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
+    r = subprocess.run(argv, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, env=env)
     wall = time.perf_counter() - t0
     if r.returncode != 0:
         raise SystemExit(f"consensus_bench: `{cmd}` from {root} exited {r.returncode} after "
@@ -122,7 +135,14 @@ def main():
     ap.add_argument("--dedup_timing", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dedup_ji", type=float, default=None, metavar="T",
                     help="time consensus --dedup_ji T against plain consensus (see above)")
-    ap.add_argument("--out", default=None, help="--dedup_ji: also write the JSON result here")
+    ap.add_argument("--with_min_pickers", type=int, default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--tiers_timing", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--min_pickers", type=int, default=None, metavar="M",
+                    help="time consensus --min_pickers M against plain consensus (see above)")
+    ap.add_argument("--baseline-lib", default=None,
+                    help="--min_pickers: librepic_gc.so of the baseline arm (the parent commit's)")
+    ap.add_argument("--out", default=None,
+                    help="--dedup_ji / --min_pickers: also write the JSON result here")
     a = ap.parse_args()
     if a.child:
         return _child(a)
@@ -130,6 +150,8 @@ def main():
         return _members(a)
     if a.dedup_ji is not None:
         return _dedup(a)
+    if a.min_pickers is not None:
+        return _tiers(a)
 
     sys.path.insert(0, os.path.join(ROOT, "repic-copy_amd"))
     from repic_amd import synth
@@ -299,6 +321,71 @@ def _dedup(a):
     finally:
         shutil.rmtree(work, ignore_errors=True)
     path = a.out or os.path.join(ROOT, "profiles", f"consensus_dedup_f2f_{a.config}.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+def _tiers(a):
+    """--min_pickers M: baseline-library consensus | consensus | consensus --min_pickers M,
+    interleaved, then one timed run of the last."""
+    sys.path.insert(0, os.path.join(ROOT, "repic-copy_amd"))
+    from repic_amd import synth
+    cfg = synth.SynthConfig(**synth.CONFIGS[a.config], seed=0)
+    work = tempfile.mkdtemp(prefix="rgc_cons_", dir=a.workdir)
+    out = {"metric": "file-to-file seconds, BOX directories -> final .box files (1 GPU)",
+           "config": a.config, "n_mg": a.n_mg, "k": cfg.k, "repeats": a.repeats,
+           "min_pickers": a.min_pickers,
+           "baseline": "plain consensus, " + ("the baseline library" if a.baseline_lib
+                                              else "this checkout")}
+    arms = (("baseline_consensus", {"lib": a.baseline_lib}), ("consensus", {}),
+            ("consensus_tiers", {"min_pickers": a.min_pickers}))
+    try:
+        in_dir = os.path.join(work, "in")
+        synth.write_box_dirs(in_dir, cfg, a.n_mg)
+        secs = {n: [] for n, _ in arms}
+        last = {}
+        for i in range(a.repeats):
+            boxes = {}
+            for n, kw in arms:
+                d = os.path.join(work, f"{n}_{i}")
+                w, ph = _run_child("consensus", ROOT, in_dir, d, cfg.box, a.timeout, work, **kw)
+                secs[n].append(w)
+                last[n] = ph
+                boxes[n] = _boxes(d)
+                out["files_" + n] = len(os.listdir(d))
+                shutil.rmtree(d)
+            assert boxes["consensus"] == boxes["baseline_consensus"], ".box files differ from the baseline's"
+            plain, tiers = boxes["consensus"], boxes["consensus_tiers"]
+            assert sorted(plain) == sorted(tiers), "--min_pickers wrote another set of .box files"
+            bad = [f for f in plain if not tiers[f].startswith(plain[f])]
+            assert not bad, f".box files do not start with the plain file's bytes: {bad[:5]}"
+        d = os.path.join(work, "timed")
+        _, ph = _run_child("consensus", ROOT, in_dir, d, cfg.box, a.timeout, work,
+                           min_pickers=a.min_pickers, tiers_timing=True)
+        shutil.rmtree(d)
+        out["box_files"] = len(plain)
+        for n, _ in arms:
+            out[n + "_s"] = secs[n]
+            out[n + "_median_s"] = statistics.median(secs[n])
+            out[n + "_range_s"] = [min(secs[n]), max(secs[n])]
+            for key in ("h2d_bytes", "d2h_bytes", "device_s", "write_s", "cliques", "picks"):
+                out[f"{n}_{key}"] = last[n].get(key)
+        lo, hi = out["baseline_consensus_range_s"]
+        out["plain_median_inside_baseline_range"] = lo <= out["consensus_median_s"] <= hi
+        out["plain_bytes_identical_to_baseline"] = (
+            out["consensus_h2d_bytes"] == out["baseline_consensus_h2d_bytes"]
+            and out["consensus_d2h_bytes"] == out["baseline_consensus_d2h_bytes"])
+        out["added_median_s"] = out["consensus_tiers_median_s"] - out["consensus_median_s"]
+        tl = last["consensus_tiers"]
+        out["picks_per_tier"] = {k_[len("picks_tier_"):]: v for k_, v in sorted(tl.items())
+                                 if k_.startswith("picks_tier_")}
+        out["kernel_ms"] = {k_[:-3]: round(v, 3) for k_, v in ph.items() if k_.endswith("_ms")}
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+    path = a.out or os.path.join(ROOT, "profiles", f"consensus_tiers_f2f_{a.config}.json")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
         json.dump(out, f, indent=1)
