@@ -24,6 +24,9 @@
  *                    <- what get_cliques --multi_out + run_ilp.py:93-119 are meant to give and
  *                       never do (run_ilp raises on such inputs): per written pick its member
  *                       from every picker, and every picker's boxes left out of the picks
+ *   rgc_agreement    <- get_cliques.py:59-69 get_jaccard as a report (beyond the reference): per
+ *                       box which pickers have a box joined to it, per picker pair the joined
+ *                       pairs, supported boxes and reciprocal best partners
  *
  * Conventions: plain pointers and sizes, no torch types.  Returns 0 on success and a
  * negative code on error (message in rgc_last_error(), thread-local).  Outputs are owned
@@ -154,7 +157,7 @@ int rgc_run(rgc_ctx* ctx, const rgc_batch_in* in, rgc_batch_out* out);
  * host once per clique level, so a second context on its own stream keeps the device busy
  * meanwhile), and one whose micrographs need a second pass re-runs that path inside rgc_wait.
  * Outputs stay valid until the next submit/run on the same context.  While a submitted
- * run awaits rgc_wait, rgc_submit, rgc_run, rgc_score_pairs, rgc_score_sweep, rgc_score_match, rgc_score_match_sweep, rgc_nms and rgc_ilp_solve on the same
+ * run awaits rgc_wait, rgc_submit, rgc_run, rgc_score_pairs, rgc_score_sweep, rgc_score_match, rgc_score_match_sweep, rgc_nms, rgc_agreement and rgc_ilp_solve on the same
  * context fail (negative return, rgc_last_error says why). */
 int rgc_submit(rgc_ctx* ctx, const rgc_batch_in* in);
 int rgc_wait(rgc_ctx* ctx, rgc_batch_out* out);
@@ -296,6 +299,63 @@ int rgc_nms(rgc_ctx* ctx, const rgc_nms_in* in, uint8_t* keep /* [n] */,
             int64_t* kept /* [n_seg] */);
 /* Bytes the last rgc_nms on ctx copied to and from the device (0, 0 when it launched nothing). */
 int rgc_nms_last_bytes(rgc_ctx* ctx, int64_t* h2d, int64_t* d2h);
+
+/* Picker agreement (beyond the reference): how much the pickers of a batch agree, per box and per
+ * picker pair.  The batch layout is rgc_batch_in's: segment s = m*k + p holds the boxes of picker
+ * p of micrograph m in file order, squares of side box_size with corner (x, y) in f64.  Two boxes
+ * b, c of the same micrograph and different pickers are joined iff |x_b - x_c| <= box_size and the
+ * reference quotient exceeds the threshold, strictly: get_jaccard (get_cliques.py:59-69) on
+ * calc_jaccard (:40-46) in its f64 operation order (no FMA, one division) - exactly the edge set
+ * of the consensus graph at that threshold.  The quotient is symmetric in its two boxes bit for
+ * bit, so "joined" is symmetric; a box with a non-finite coordinate is joined to nothing (the
+ * formula yields 0 or NaN there).  N = box_off[n_mg*k]; indices are batch box indices.
+ *   support[b]              bit q set iff b is joined to at least one box of picker q (never the
+ *                           bit of b's own picker)
+ *   partner[b*k+q]          the box of picker q joined to b with the largest JI, ties to the
+ *                           lowest batch index; -1 if none, and for b's own picker
+ *   partner_ji[b*k+q]       that partner's JI, bit for bit the reference quotient; 0.0 where
+ *                           partner is -1
+ *   pair_edges[(m*k+p)*k+q]     joined pairs between segments (m,p) and (m,q): symmetric,
+ *                               diagonal 0
+ *   pair_supported[(m*k+p)*k+q] boxes of (m,p) whose bit q is set (directed), diagonal 0
+ *   pair_mutual[(m*k+p)*k+q]    boxes b of (m,p) with c = partner[b][q] >= 0 and
+ *                               partner[c][p] == b: reciprocal best partners, a one-to-one
+ *                               pairing, symmetric and deterministic (not a maximum matching)
+ * Every output is a function of the inputs alone.  The outputs are host memory owned by the
+ * context, valid until its next call.  Without RGC_F_PARTNERS partner / partner_ji are NULL and
+ * never leave the device: the call copies back 1 B per box and 24 k^2 B per micrograph.
+ * n_mg == 0 and all-empty batches are valid and launch nothing (n_mg == 0: every pointer NULL);
+ * k == 1: every mask 0, every partner -1.  One workgroup per segment with a finite box, two
+ * launches; RGC_F_TIMING records "k_agree_partner" and "k_agree_mutual".
+ * Refused before any launch, the context staying usable: null arguments with boxes to read, a
+ * submitted run awaiting rgc_wait, n_mg < 0 or n_mg*k above INT32_MAX, k outside 1..8, offsets
+ * that do not start at 0 or decrease, more than 2^31 - 1 boxes, box_size outside 1..2^26, a
+ * threshold that is NaN or outside [0, 1).
+ * Additive symbols: no struct changes layout and RGC_ABI_VERSION stays 11; a caller finds out
+ * whether the library has them by looking the symbols up. */
+#define RGC_F_PARTNERS 2048u     /* rgc_agree_in.flags: also return partner / partner_ji */
+typedef struct rgc_agree_in {
+  int32_t n_mg;
+  int32_t k;                /* 1..8 */
+  int64_t box_size;         /* 1..2^26 */
+  double ji_threshold;      /* finite, 0 <= t < 1 */
+  uint32_t flags;           /* RGC_F_TIMING | RGC_F_PARTNERS */
+  const int64_t* box_off;   /* HOST [n_mg*k+1], starts at 0, non-decreasing */
+  const double* x;          /* HOST [N] */
+  const double* y;
+} rgc_agree_in;
+typedef struct rgc_agree_out {
+  uint8_t* support;         /* [N] */
+  int32_t* partner;         /* [N*k], NULL without RGC_F_PARTNERS */
+  double* partner_ji;       /* [N*k], NULL without RGC_F_PARTNERS */
+  int64_t* pair_edges;      /* [n_mg*k*k] */
+  int64_t* pair_supported;
+  int64_t* pair_mutual;
+} rgc_agree_out;
+int rgc_agreement(rgc_ctx* ctx, const rgc_agree_in* in, rgc_agree_out* out);
+/* Bytes the last rgc_agreement on ctx copied to and from the device (0, 0 when it launched
+ * nothing). */
+int rgc_agreement_last_bytes(rgc_ctx* ctx, int64_t* h2d, int64_t* d2h);
 
 /* run_ilp (repic/commands/run_ilp.py:50-63): maximise w.x over binary x subject to A x <= 1,
  * exactly, for a batch of micrographs at once (rows are global box ids: micrographs never

@@ -116,6 +116,14 @@ int collect_times(rgc_ctx* c, bool keep, bool tail) {
   return 0;
 }
 
+int section_time(rgc_ctx* c, hipEvent_t e0, hipEvent_t e1, const char* name) {
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+  c->times.push_back(ms);
+  c->time_names.push_back(name);
+  return 0;
+}
+
 extern "C" {
 
 int rgc_abi_version(void) { return RGC_ABI_VERSION; }

@@ -81,6 +81,9 @@ enum DevBufId {
   D_VT_BOXOFF, D_VT_TIER, D_VT_SEGCNT, D_VT_PSEG, D_VT_PBOXOFF, D_VT_GX, D_VT_GY, D_VT_GS,
   D_VT_ORIGIN, D_VT_QMETA, D_VT_CW, D_VT_CCONF, D_VT_CCONS, D_VT_CMEMB, D_VT_CMASK, D_VT_COLOFF,
   D_VT_PCX, D_VT_PCY, D_VT_PW, D_VT_PMASK, D_VT_PMEMB, D_VT_BAD, D_VT_HXYS, D_VT_HPOFF,
+  // picker agreement (rgc_agree.hip): offsets, finite counts, launch list, coordinates in x
+  // order with their indices, then the outputs: masks, partners, their JI, the pair matrices
+  D_AG_OFF, D_AG_NS, D_AG_SEG, D_AG_SXY, D_AG_SIDX, D_AG_SUP, D_AG_PART, D_AG_PJI, D_AG_PAIR,
   D_COUNT
 };
 enum HostBufId {
@@ -95,7 +98,9 @@ enum HostBufId {
   // consensus --min_pickers: the per-micrograph block (tier k's run stats, pick_off, the ILP
   // summary, per-tier counts), the pick block, box_tier, staging of counts and per-pick arrays,
   // and the gather hook's outputs
-  H_VT_MG, H_VT_PICK, H_VT_BOXTIER, H_VT_STAGE, H_VT_SUB, H_VT_ORIGIN, H_VT_GXYS, H_COUNT
+  H_VT_MG, H_VT_PICK, H_VT_BOXTIER, H_VT_STAGE, H_VT_SUB, H_VT_ORIGIN, H_VT_GXYS,
+  // rgc_agreement: one block (pair matrices, partner_ji, partner, support)
+  H_AG_OUT, H_COUNT
 };
 
 struct Buf {
@@ -150,6 +155,7 @@ struct rgc_ctx {
   std::string pend_err;          // the worker's error message (g_err is per thread)
   int64_t fix_fetch_bytes = 0;   // rgc_consensus: CSC bytes fetched for reduced-cost fixing
   int64_t nms_h2d = 0, nms_d2h = 0;   // rgc_nms: bytes the last call copied (rgc_nms_last_bytes)
+  int64_t agree_h2d = 0, agree_d2h = 0;   // rgc_agreement: likewise (rgc_agreement_last_bytes)
 };
 
 // ---- arena, events (rgc_ctx.cpp)
@@ -167,6 +173,17 @@ int mark(rgc_ctx* c, const char* name);
 // are replaced); tail: the last mark's section runs to ev_tail (else the last mark only
 // closes the one before it).
 int collect_times(rgc_ctx* c, bool keep, bool tail);
+// RGC_F_TIMING of the entry points that time a few launches of one call (rgc_nms,
+// rgc_agreement): events that live as long as the call ...
+struct CallEvents {
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  ~CallEvents() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+// ... and the section between two of them appended to c->times as `name`
+int section_time(rgc_ctx* c, hipEvent_t e0, hipEvent_t e1, const char* name);
 
 template <typename T>
 inline T* D(rgc_ctx* c, int id) { return reinterpret_cast<T*>(c->d[id].p); }

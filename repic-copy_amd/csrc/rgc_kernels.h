@@ -423,6 +423,31 @@ constexpr int NMS_ST_LIST = 2;       // a conflict list names a box that is not 
 void launch_nms_count(hipStream_t stream, int n_seg, const NmsArgs& A);
 void launch_nms(hipStream_t stream, int n_seg, const NmsArgs& A);
 
+// picker agreement (rgc_agree.hip): one workgroup per launched segment.  Segment s = m * k + p
+// holds the boxes [off[s], off[s + 1]) of picker p of micrograph m.  sx / sy / sidx hold, in the
+// first ns[s] slots of the segment's range, its boxes with finite coordinates in ascending x and
+// their index within the segment.  seg lists the launched segments (ns > 0).  The host presets
+// support / pair_* to 0, partner to -1 and partner_ji to 0: the kernels write only what differs.
+struct AgreeArgs {
+  int k;
+  int64_t n_box;
+  const int64_t* off;         // [n_mg * k + 1]
+  const int32_t* ns;          // [n_mg * k]
+  const int32_t* seg;         // [launched segments]
+  const double* sx;
+  const double* sy;
+  const int32_t* sidx;
+  double B, two_b2, t;        // joined <=> is_edge(..., B, two_b2, t)
+  uint8_t* support;           // [n_box]
+  int32_t* partner;           // [n_box * k] batch box index, -1
+  double* partner_ji;         // [n_box * k], or nullptr: not asked for
+  int64_t* pair_edges;        // [n_mg * k * k]
+  int64_t* pair_supported;
+  int64_t* pair_mutual;
+};
+void launch_agree_partner(hipStream_t stream, int n_launch, const AgreeArgs& A);
+void launch_agree_mutual(hipStream_t stream, int n_launch, const AgreeArgs& A);
+
 // run_ilp exact set packing (rgc_ilp.hip)
 struct IlpArgs {
   int64_t n_cols, n_rows, n_comp;

@@ -12,23 +12,6 @@ namespace {
 
 constexpr int64_t NMS_BOX_MAX = (int64_t)1 << 26;
 
-struct NmsEvents {
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  ~NmsEvents() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-
-// the section between two events as `name` (RGC_F_TIMING)
-int nms_time(rgc_ctx* c, hipEvent_t e0, hipEvent_t e1, const char* name) {
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  c->times.push_back(ms);
-  c->time_names.push_back(name);
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int rgc_nms(rgc_ctx* c, const rgc_nms_in* in, uint8_t* keep, int64_t* kept) {
@@ -133,7 +116,7 @@ extern "C" int rgc_nms(rgc_ctx* c, const rgc_nms_in* in, uint8_t* keep, int64_t*
   A.kept = D<int64_t>(c, D_NM_KEPT);
   A.status = D<int32_t>(c, D_NM_STAT);
   const bool timing = (in->flags & RGC_F_TIMING) != 0;
-  NmsEvents E;
+  CallEvents E;
   if (timing)
     for (hipEvent_t& e : E.ev) HIPCHK(hipEventCreate(&e));
 
@@ -169,8 +152,8 @@ extern "C" int rgc_nms(rgc_ctx* c, const rgc_nms_in* in, uint8_t* keep, int64_t*
   HIPCHK(hipStreamSynchronize(s));
   c->nms_d2h += n + np * 12;
   if (timing) {
-    TRY(nms_time(c, E.ev[0], E.ev[1], "k_nms_count"));
-    TRY(nms_time(c, E.ev[2], E.ev[3], "k_nms"));
+    TRY(section_time(c, E.ev[0], E.ev[1], "k_nms_count"));
+    TRY(section_time(c, E.ev[2], E.ev[3], "k_nms"));
   }
   for (int64_t q = 0; q < np; ++q)
     if (status[q] != 0)

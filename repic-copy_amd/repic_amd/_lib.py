@@ -161,6 +161,35 @@ if has_nms():
     lib.rgc_nms.argtypes = [C.c_void_p, C.POINTER(NmsIn), C.c_void_p, C.c_void_p]
     lib.rgc_nms_last_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
 
+F_PARTNERS = 2048   # rgc_agreement: also return partner / partner_ji
+
+
+class AgreeIn(C.Structure):
+    _fields_ = [("n_mg", C.c_int32), ("k", C.c_int32), ("box_size", C.c_int64),
+                ("ji_threshold", C.c_double), ("flags", C.c_uint32), ("box_off", C.c_void_p),
+                ("x", C.c_void_p), ("y", C.c_void_p)]
+
+
+class AgreeOut(C.Structure):
+    _fields_ = [("support", _u8p), ("partner", _i32p), ("partner_ji", _f64p),
+                ("pair_edges", _i64p), ("pair_supported", _i64p), ("pair_mutual", _i64p)]
+
+
+AGREE_SYMBOLS = ("rgc_agreement", "rgc_agreement_last_bytes")
+
+
+def has_agreement() -> bool:
+    """The loaded library has the picker-agreement entry points (additive symbols: the ABI
+    version does not tell)."""
+    return all(hasattr(lib, n) for n in AGREE_SYMBOLS)
+
+
+if has_agreement():
+    lib.rgc_agreement.argtypes = [C.c_void_p, C.POINTER(AgreeIn), C.POINTER(AgreeOut)]
+    lib.rgc_agreement_last_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_int64)]
+
+
 class TiersOut(C.Structure):
     _fields_ = [("n_tiers", C.c_int32), ("ptier", _i32p), ("pmask", _i32p), ("pw", _f32p),
                 ("pmember", _i32p), ("box_tier", _i32p), ("tier_cols", _i64p),
@@ -244,7 +273,7 @@ EXPORTS = ["rgc_abi_version", "rgc_last_error", "rgc_device_count", "rgc_ctx_cre
            "rgc_score_pairs", "rgc_score_sweep", "rgc_score_match", "rgc_score_match_sweep", "rgc_test_iou_edge", "rgc_ilp_solve", "rgc_write_outputs", "rgc_pickle_bytes",
            "rgc_py_float_repr", "rgc_consensus", "rgc_pick_select", "rgc_write_boxes",
            "rgc_np_float_str", "rgc_test_ji_cutoff", *MEMBERS_SYMBOLS, *NMS_SYMBOLS,
-           *TIERS_SYMBOLS]
+           *TIERS_SYMBOLS, *AGREE_SYMBOLS]
 
 
 class RGCError(RuntimeError):
@@ -401,6 +430,8 @@ class Context:
         self.device = device
         self._pending = None
         self._lease = None   # weakref to the _HostLease of the last Result
+        # (H2D, D2H) bytes of the last nms / agreement call
+        self.nms_bytes = self.agreement_bytes = (0, 0)
 
     def set_copy_stream(self, stream: int):
         """Stream of the per-micrograph stats copy of non-lazy submits (0: the null stream);
@@ -693,6 +724,36 @@ class Context:
         self.nms_bytes = (h2d.value, d2h.value)
         return keep, kept
 
+    def agreement(self, n_mg, k, box_size, box_off, x, y, ji_threshold=None, partners=False,
+                  timing=False):
+        """Picker agreement of a batch in ``rgc_batch_in``'s layout (rgc_agreement): two boxes
+        of one micrograph and different pickers are joined iff ``|dx| <= box_size`` and the
+        reference's f64 Jaccard quotient exceeds ``ji_threshold`` (None: the reference's 0.3),
+        strictly.  -> :class:`Agreement`; ``partners`` also returns the best partner of every
+        box per picker (the only mode in which they leave the device).  ``agreement_bytes`` then
+        holds the (H2D, D2H) bytes the call copied.  The context's other host buffers are not
+        touched: a Result stays valid."""
+        _need_agreement()
+        box_off = np.ascontiguousarray(box_off, np.int64)
+        x = np.ascontiguousarray(x, np.float64)
+        y = np.ascontiguousarray(y, np.float64)
+        n_mg, k = int(n_mg), int(k)
+        # (what the library reads must be there; what it refuses unread is left to it)
+        valid = n_mg > 0 and 1 <= k <= MAX_K and n_mg * k <= 2 ** 31 - 1
+        assert box_off.ndim == 1 and (not valid or len(box_off) == n_mg * k + 1)
+        n = int(box_off[-1]) if valid else 0
+        assert x.shape == y.shape and x.ndim == 1 and (n > 2 ** 31 - 1 or len(x) >= n)
+        t = JI_DEFAULT if ji_threshold is None else float(ji_threshold)
+        flags = (F_TIMING if timing else 0) | (F_PARTNERS if partners else 0)
+        ai = AgreeIn(n_mg, k, int(box_size), t, flags, box_off.ctypes.data, x.ctypes.data,
+                     y.ctypes.data)
+        ao = AgreeOut()
+        _check(lib.rgc_agreement(self._p, C.byref(ai), C.byref(ao)))
+        h2d, d2h = C.c_int64(0), C.c_int64(0)
+        _check(lib.rgc_agreement_last_bytes(self._p, C.byref(h2d), C.byref(d2h)))
+        self.agreement_bytes = (h2d.value, d2h.value)
+        return Agreement(ao, n_mg, k, n, partners)
+
     def last_edges(self):
         """Test hook: (u, v, ji) copies of the JI > threshold edges of the last run with F_EDGES
         (batch box indices; order unspecified)."""
@@ -819,6 +880,30 @@ def _need_nms():
     if not has_nms():
         raise RGCError(f"{LIB_PATH} has no greedy-NMS entry points "
                        f"({', '.join(NMS_SYMBOLS)}): rebuild it")
+
+
+def _need_agreement():
+    if not has_agreement():
+        raise RGCError(f"{LIB_PATH} has no picker-agreement entry points "
+                       f"({', '.join(AGREE_SYMBOLS)}): rebuild it")
+
+
+class Agreement:
+    """One rgc_agreement call, as numpy copies.  ``support`` uint8 [N]: bit q set iff the box is
+    joined to a box of picker q; ``partner`` int32 [N, k] / ``partner_ji`` f64 [N, k] (None
+    without ``partners``): the joined box of picker q with the largest JI (ties: the lowest batch
+    index; -1 / 0.0 without one); ``pair_edges`` / ``pair_supported`` / ``pair_mutual`` int64
+    [n_mg, k, k]: joined pairs, boxes of (m, p) supported by q, reciprocal best partners."""
+
+    def __init__(self, ao: AgreeOut, n_mg, k, n, partners):
+        self.n_mg, self.k = n_mg, k
+        self.support = _copy(ao.support, n, np.uint8)
+        self.partner = self.partner_ji = None
+        if partners:
+            self.partner = _copy(ao.partner, n * k, np.int32).reshape(n, k)
+            self.partner_ji = _copy(ao.partner_ji, n * k, np.float64).reshape(n, k)
+        for f in ("pair_edges", "pair_supported", "pair_mutual"):
+            setattr(self, f, _copy(getattr(ao, f), n_mg * k * k, np.int64).reshape(n_mg, k, k))
 
 
 def np_float_str(v) -> str:
